@@ -2,13 +2,19 @@
 (50k nodes x 100k pods, 70% LS / 30% BE, Fit + LoadAware with the shipped
 scheduler profile) through libkoordhip.so, on N GPUs of one node.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: torch.distributed.run, one rank per GPU, RCCL over xGMI)
 
 A step = one full greedy pass of the pod stream over the node table, starting
 from the same snapshot (device-side restore of the mutable columns, ~5 MB of
 D2D copies, inside the timed region).  Inputs are HBM-resident before timing.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline
+fields.  `--dump-outputs DIR` also writes what the last timed step computed
+(DIR/<name>.npy).  `--full` adds everything that takes runs of its own: the
+per-kernel roofline objects (one more step with HIP events around every
+launch), the per-cycle latency leg, the CPU baseline and `--check`.
 """
 import argparse
 import json
@@ -177,6 +183,129 @@ def latency_leg(eng, pods, ext=None, reps=200):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def fetch_outputs(eng, n_pods: int, cpusets=False, devices=False) -> dict:
+    """What a caller of the timed path (koordhip_place_staged) receives from
+    its last call: the node of every pod (-1 = unschedulable), and where the
+    workload has them the cpuset each cpuset pod was given and the device slots
+    each device pod was given."""
+    out = {"placements": eng.fetch_placements(n_pods)}
+    if cpusets:
+        out["cpusets"] = eng.fetch_cpusets(n_pods)
+    if devices:
+        out["devices"] = eng.fetch_devices(n_pods)
+    return out
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """`--dump-outputs DIR`: DIR/<name>.npy in float64, one file per array of
+    fetch_outputs.  Every value is an integer below 2^53 (a 64-bit mask is
+    split into its low and high 32-bit words along a new last axis), so float64
+    holds it exactly.  An array over its share of the 64 MB budget is cut to a
+    fixed, seeded sample of its rows."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.uint64:
+            a = a.view(np.uint32).reshape(a.shape + (2,))
+        a = a.astype(np.float64)
+        row = max(a[0].nbytes, 1) if a.ndim > 1 and len(a) else 8
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), size=share // row, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def roofline_objects(args, ks, kn, pods, cfg, ext, elapsed, batch, lag) -> dict:
+    """`--full`: the per-kernel objects of the result line (`roofline`,
+    `eval_roofline`, `select`, the device pods' traffic), from the kernel stats
+    of the extra step run with HIP events around every launch."""
+    pods_profiled = args.pods
+    k = (lag + 1) * batch   # list length: the resolve re-checks the nodes of the last `lag` rounds
+    # ---- the dominant kernel: k_resolve, the sequential greedy (one persistent
+    #      launch per step spanning the round pipeline).  Algorithmic bytes per
+    #      pod (DESIGN.md §5): its list (k x 8 B) + pod record (96 B) + the
+    #      prefetched list-head rows (128 / batch rows x 160 B) + one row
+    #      write-back (13 mutable columns, 100 B).
+    heads = max(1, 128 // batch)
+    b_pod = k * 8 + 96 + heads * 160 + 100
+    persistent = ks["resolve_launches"] <= 1
+    # a persistent resolve spans the whole step: its launch time is the timed
+    # step itself (an upper bound), never the separately instrumented step
+    res_s = (elapsed / args.steps) if persistent else ks["resolve_ms"] * 1e-3 / max(ks["resolve_launches"], 1)
+    pods_per_launch = pods_profiled / max(ks["resolve_launches"], 1)
+    res_gbs = pods_per_launch * b_pod / res_s / 1e9 if res_s > 0 else None
+    # ---- the evaluation kernel k_scan: physical bytes per launch = the node
+    #      columns the round's pods consult, read once (VGPR-resident across the
+    #      pod loop), + the u16 score-matrix row per (pod, node) + chunk maxima
+    b_eval = bytes_per_eval(pods, cfg)
+    scan_us = ks["scan_ms"] * 1e3 / max(ks["scan_launches"], 1)
+    evals_per_launch = ks["evals"] / max(ks["rounds"], 1)   # one scan launch per round (the timed ones are a sample)
+    pods_per_round = evals_per_launch / max(args.nodes, 1)
+    col_bytes = float(b_eval.max()) * args.nodes
+    # the fused k_eval_topk (no select launches) keeps the scores in LDS: its
+    # physical bytes are the node columns once (+ the small slice lists); the
+    # split k_scan also writes the u16 score matrix and the chunk maxima
+    fused = ks["select_launches"] == 0
+    phys = col_bytes if fused else col_bytes + pods_per_round * args.nodes * 2 + pods_per_round * args.nodes / 64 * 2
+    scan_gbs = phys / (scan_us * 1e-6) / 1e9 if scan_us > 0 else None
+    traffic, traffic_src, traffic_kernel, pmc_kernels = pmc_traffic(args.workload)
+    if traffic_src is not None and traffic_kernel != kn["eval"]:
+        traffic, traffic_src = None, (f"none for {kn['eval']} (the committed PMC summary is of "
+                                      f"{traffic_kernel or 'an unnamed kernel'})")
+    cls = kn["eval"].startswith("kh::k_cls_run")
+    if cls:
+        # class-incremental lists (cls.hip): one persistent workgroup per pod
+        # class for the whole step, builds (k_scan over the class records +
+        # k_cls_collect) in batches on the second stream
+        raw = np.ascontiguousarray(pods).view(np.uint8).reshape(len(pods), -1)
+        ncls = int(len(np.unique(raw, axis=0)))
+        bld_us = ks["select_ms"] * 1e3 / max(ks["select_launches"], 1)
+        eval_obj = {"bound": "latency", "kernel": kn["eval"],
+                    "mode": "class-incremental lists: one persistent workgroup per pod class keeps its best "
+                            f"{2048} keys in LDS and re-evaluates only the nodes the resolve committed since its "
+                            "last round (the commit log); the lists are exact top-k keys like k_scan + select's",
+                    "classes": ncls, "avg_launch_ms": round(ks["scan_ms"] / max(ks["scan_launches"], 1), 3),
+                    "timing": "HIP events around the persistent launch (the whole step)",
+                    "builds": {"kernels": "k_scan over the class records + k_cls_collect",
+                               "timed_batches": int(ks["select_launches"]), "avg_batch_us": round(bld_us, 3),
+                               "traffic": {k: v["hbm_bytes_per_launch"] for k, v in pmc_kernels.items()
+                                           if "class build" in k or "k_cls_collect" in k} or None},
+                    "executed_evals_per_step": int(ks["executed_evals"]),
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "traffic_note": "HBM bytes of one k_cls_run launch (the whole stream's class workgroups) "
+                                    "from the PMC replay (scripts/pmc_summary.py), of the stream size it was "
+                                    "collected on"}
+    out = {
+        "roofline": {"bound": "latency", "kernel": kn["resolve"],
+                     "limiter": "latency: one workgroup's sequential greedy (not bandwidth); priced against HBM peak",
+                     "timing": "the timed step (persistent launch)" if persistent else "HIP events per launch",
+                     "achieved": round(res_gbs, 3) if res_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(res_gbs / HBM_PEAK_GBS, 6) if res_gbs else None, "traffic": None,
+                     "bytes_per_pod": b_pod, "avg_launch_ms": round(res_s * 1e3, 3),
+                     "pods_per_launch": pods_per_launch,
+                     "us_per_pod": round(res_s * 1e6 / max(pods_per_launch, 1), 4)},
+        "eval_roofline": eval_obj if cls else {"bound": "hbm", "kernel": kn["eval"],
+                          "achieved": round(scan_gbs, 1) if scan_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": round(scan_gbs / HBM_PEAK_GBS, 4) if scan_gbs else None,
+                          "traffic": traffic, "traffic_source": traffic_src,
+                          "bytes_per_launch": round(phys), "avg_launch_us": round(scan_us, 3),
+                          "evals_per_launch": evals_per_launch,
+                          "algorithmic_bytes_per_eval": round(float(b_eval.mean()), 2),
+                          "algorithmic_GBps": round(evals_per_launch * float(b_eval.mean()) / (scan_us * 1e-6) / 1e9, 1)
+                          if scan_us > 0 else None},
+    }
+    if not cls:
+        out["select"] = {"kernel": "(in k_eval_topk)" if fused else "k_select_split",
+                         "avg_launch_us": round(ks["select_ms"] * 1e3 / max(ks["select_launches"], 1), 3)}
+    if ext is not None:
+        out["device_pods_traffic"] = {k: v["hbm_bytes_per_launch"] for k, v in pmc_kernels.items() if "k_ext_" in k} or None
+    return out
+
+
 def launch_ranks(n: int) -> int:
     """`--gpus N > 1` without a torch.distributed launcher: start one as a CHILD
     process (nothing here has touched the GPU yet) with this command line, and
@@ -218,9 +347,17 @@ def main():
     ap.add_argument("--batch", type=int, default=0)
     ap.add_argument("--dev-frac", type=float, default=None,
                     help="deviceshare / config4dsmix workloads: share of pods requesting GPUs (default 0.2 / 0.02)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float64): placements [pods] (node index, -1 = unschedulable), and where the workload "
+                         "has them cpusets [pods][words][lo, hi] and devices [pods][types]")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the per-kernel roofline objects (one more, untimed step with HIP "
+                         "events around every launch), the per-cycle latency leg, the CPU baseline and --check; "
+                         "--no-cpu-baseline / --cpu-budget / --no-latency / --check shape this part")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--check", action="store_true", help="verify placements vs the oracle (slow)")
+    ap.add_argument("--check", action="store_true", help="--full: verify placements vs the oracle (slow)")
     ap.add_argument("--one-rank-comm", action="store_true",
                     help="N=1 only: attach a one-rank RCCL communicator, so every round takes the multi-GPU "
                          "exchange path (all-gather + merge) -- measures that pipeline on one GPU")
@@ -237,6 +374,8 @@ def main():
     ap.add_argument("--probe-ranks", action="store_true",
                     help="print this rank's RANK / WORLD_SIZE and exit before any GPU work (launcher test)")
     args = ap.parse_args()
+    if args.check and not args.full:
+        ap.error("--check is part of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -334,14 +473,19 @@ def main():
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    # per-kernel split for the roofline: one more (untimed) step with HIP
-    # events around every launch (they cost a few us per round, so the timed
-    # steps run without them)
-    eng.set_profile_kernels(True)
-    step()
-    ks = eng.kernel_stats()
+    dump = args.dump_outputs is not None and rank == 0
+    outputs = fetch_outputs(eng, len(pods), cpusets=dump and numa, devices=dump and dsmix)   # the last timed step's
+    ks = eng.kernel_stats()          # the last timed step's counters (no per-launch events: the *_ms are zero)
     kn = eng.kernel_names()
-    eng.set_profile_kernels(False)
+    if args.full:
+        # per-kernel split for the roofline: one more (untimed) step with HIP
+        # events around every launch (they cost a few us per round, so the timed
+        # steps run without them)
+        eng.set_profile_kernels(True)
+        step()
+        ks = eng.kernel_stats()
+        kn = eng.kernel_names()
+        eng.set_profile_kernels(False)
     executed = float(ks["executed_evals"])   # this rank's, per step
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
@@ -350,8 +494,8 @@ def main():
         te = torch.tensor([executed], dtype=torch.float64, device="cuda")
         dist.all_reduce(te, op=dist.ReduceOp.SUM)   # every rank's evaluations (a local rank runs the full table)
         executed = float(te.item())
-    placements = eng.fetch_placements(len(pods))
-    lat = latency_leg(eng, pods, ext) if (world == 1 and not args.no_latency) else None
+    placements = outputs["placements"]
+    lat = latency_leg(eng, pods, ext) if (args.full and world == 1 and not args.no_latency) else None
 
     if rank != 0:
         if dist is not None:
@@ -360,7 +504,6 @@ def main():
         return
 
     pods_total = args.pods * args.steps * (world if world > 1 and not shard else 1)  # replicas: every rank's stream
-    pods_profiled = args.pods
     # equivalent evaluations: every (pod, node) pair of the schedule decided
     # exactly (what a full Filter + Score pass per pod computes); executed: the
     # (pod, node) evaluations the kernels actually ran (class-list builds +
@@ -371,61 +514,6 @@ def main():
     value = pods_total / elapsed
     batch = int(ks["round_pods"]) or eng.cfg.batch_pods or (16 if numa else 32)
     lag = int(ks["lag"]) or 1
-    k = (lag + 1) * batch   # list length: the resolve re-checks the nodes of the last `lag` rounds
-    # ---- the dominant kernel: k_resolve, the sequential greedy (one persistent
-    #      launch per step spanning the round pipeline).  Algorithmic bytes per
-    #      pod: its list (k x 8 B) + pod record (96 B) + the
-    #      prefetched list-head rows (128 / batch rows x 160 B) + one row
-    #      write-back (13 mutable columns, 100 B).
-    heads = max(1, 128 // batch)
-    b_pod = k * 8 + 96 + heads * 160 + 100
-    persistent = ks["resolve_launches"] <= 1
-    # a persistent resolve spans the whole step: its launch time is the timed
-    # step itself (an upper bound), never the separately instrumented step
-    res_s = (elapsed / args.steps) if persistent else ks["resolve_ms"] * 1e-3 / max(ks["resolve_launches"], 1)
-    pods_per_launch = pods_profiled / max(ks["resolve_launches"], 1)
-    res_gbs = pods_per_launch * b_pod / res_s / 1e9 if res_s > 0 else None
-    # ---- the evaluation kernel k_scan: physical bytes per launch = the node
-    #      columns the round's pods consult, read once (VGPR-resident across the
-    #      pod loop), + the u16 score-matrix row per (pod, node) + chunk maxima
-    b_eval = bytes_per_eval(pods, cfg)
-    scan_us = ks["scan_ms"] * 1e3 / max(ks["scan_launches"], 1)
-    evals_per_launch = ks["evals"] / max(ks["rounds"], 1)   # one scan launch per round (the timed ones are a sample)
-    pods_per_round = evals_per_launch / max(args.nodes, 1)
-    col_bytes = float(b_eval.max()) * args.nodes
-    # the fused k_eval_topk (no select launches) keeps the scores in LDS: its
-    # physical bytes are the node columns once (+ the small slice lists); the
-    # split k_scan also writes the u16 score matrix and the chunk maxima
-    fused = ks["select_launches"] == 0
-    phys = col_bytes if fused else col_bytes + pods_per_round * args.nodes * 2 + pods_per_round * args.nodes / 64 * 2
-    scan_gbs = phys / (scan_us * 1e-6) / 1e9 if scan_us > 0 else None
-    traffic, traffic_src, traffic_kernel, pmc_kernels = pmc_traffic(args.workload)
-    if traffic_src is not None and traffic_kernel != kn["eval"]:
-        traffic, traffic_src = None, (f"none for {kn['eval']} (the committed PMC summary is of "
-                                      f"{traffic_kernel or 'an unnamed kernel'})")
-    cls = kn["eval"].startswith("kh::k_cls_run")
-    if cls:
-        # class-incremental lists (cls.hip): one persistent workgroup per pod
-        # class for the whole step, builds (k_scan over the class records +
-        # k_cls_collect) in batches on the second stream
-        raw = np.ascontiguousarray(pods).view(np.uint8).reshape(len(pods), -1)
-        ncls = int(len(np.unique(raw, axis=0)))
-        bld_us = ks["select_ms"] * 1e3 / max(ks["select_launches"], 1)
-        eval_obj = {"bound": "latency", "kernel": kn["eval"],
-                    "mode": "class-incremental lists: one persistent workgroup per pod class keeps its best "
-                            f"{2048} keys in LDS and re-evaluates only the nodes the resolve committed since its "
-                            "last round (the commit log); the lists are exact top-k keys like k_scan + select's",
-                    "classes": ncls, "avg_launch_ms": round(ks["scan_ms"] / max(ks["scan_launches"], 1), 3),
-                    "timing": "HIP events around the persistent launch (the whole step)",
-                    "builds": {"kernels": "k_scan over the class records + k_cls_collect",
-                               "timed_batches": int(ks["select_launches"]), "avg_batch_us": round(bld_us, 3),
-                               "traffic": {k: v["hbm_bytes_per_launch"] for k, v in pmc_kernels.items()
-                                           if "class build" in k or "k_cls_collect" in k} or None},
-                    "executed_evals_per_step": int(ks["executed_evals"]),
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "traffic_note": "HBM bytes of one k_cls_run launch (the whole stream's class workgroups) "
-                                    "from the PMC replay (scripts/pmc_summary.py), of the stream size it was "
-                                    "collected on"}
     out = {
         "metric": METRIC,
         "value": round(value, 2),
@@ -468,43 +556,26 @@ def main():
                                    "lists; the library's fallback, one cluster's schedule)" if local
                                    else f"node-shard x{world}" + (" (one-rank RCCL exchange path)" if args.one_rank_comm and world == 1 else ""))},
         "unschedulable": int((placements < 0).sum()),
-        "latency": lat,
-        "roofline": {"bound": "latency", "kernel": kn["resolve"],
-                     "limiter": "latency: one workgroup's sequential greedy (not bandwidth); priced against HBM peak",
-                     "timing": "the timed step (persistent launch)" if persistent else "HIP events per launch",
-                     "achieved": round(res_gbs, 3) if res_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(res_gbs / HBM_PEAK_GBS, 6) if res_gbs else None, "traffic": None,
-                     "bytes_per_pod": b_pod, "avg_launch_ms": round(res_s * 1e3, 3),
-                     "pods_per_launch": pods_per_launch,
-                     "us_per_pod": round(res_s * 1e6 / max(pods_per_launch, 1), 4)},
-        "eval_roofline": eval_obj if cls else {"bound": "hbm", "kernel": kn["eval"],
-                          "achieved": round(scan_gbs, 1) if scan_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": round(scan_gbs / HBM_PEAK_GBS, 4) if scan_gbs else None,
-                          "traffic": traffic, "traffic_source": traffic_src,
-                          "bytes_per_launch": round(phys), "avg_launch_us": round(scan_us, 3),
-                          "evals_per_launch": evals_per_launch,
-                          "algorithmic_bytes_per_eval": round(float(b_eval.mean()), 2),
-                          "algorithmic_GBps": round(evals_per_launch * float(b_eval.mean()) / (scan_us * 1e-6) / 1e9, 1)
-                          if scan_us > 0 else None},
     }
-    if not cls:
-        out["select"] = {"kernel": "(in k_eval_topk)" if fused else "k_select_split",
-                         "avg_launch_us": round(ks["select_ms"] * 1e3 / max(ks["select_launches"], 1), 3)}
     if dsmix:
-        out["device_pods_traffic"] = {k: v["hbm_bytes_per_launch"] for k, v in pmc_kernels.items() if "k_ext_" in k} or None
         out["device_pods"] = {"pods": int((ext["flags"] != 0).sum()), "kernels": "k_ext_pre<0> + k_ext_final<0>",
                               "route": "pipelined (resolve hand-off)" if kn["resolve"].startswith("kh::k_resolve")
                               else "sequential cycle"}
-    if args.check:
-        import oracle
-        orc = oracle.Oracle(cfg, table)
-        ref = orc.place_stream(pods, threads=min(16, os.cpu_count() or 1)) if ext is None else \
-            orc.place_stream_ext(pods, ext, threads=min(16, os.cpu_count() or 1))
-        out["check"] = bool(np.array_equal(ref, placements))
-    if world == 1 and not args.no_cpu_baseline:
-        cb = cpu_baseline(table, pods, cfg, args.cpu_budget, ext=ext)
-        out["cpu_baseline"] = cb
-        out["speedup_vs_best_cpu_leg"] = round(value / cb["best_leg"]["pods_per_s"], 1)
+    if dump:
+        dump_outputs(args.dump_outputs, outputs)
+    if args.full:
+        out["latency"] = lat
+        out.update(roofline_objects(args, ks, kn, pods, cfg, ext, elapsed, batch, lag))
+        if args.check:
+            import oracle
+            orc = oracle.Oracle(cfg, table)
+            ref = orc.place_stream(pods, threads=min(16, os.cpu_count() or 1)) if ext is None else \
+                orc.place_stream_ext(pods, ext, threads=min(16, os.cpu_count() or 1))
+            out["check"] = bool(np.array_equal(ref, placements))
+        if world == 1 and not args.no_cpu_baseline:
+            cb = cpu_baseline(table, pods, cfg, args.cpu_budget, ext=ext)
+            out["cpu_baseline"] = cb
+            out["speedup_vs_best_cpu_leg"] = round(value / cb["best_leg"]["pods_per_s"], 1)
     print(json.dumps(out), flush=True)
     eng.close()                      # before interpreter teardown (the HIP runtime's own exit handlers)
     if dist is not None:
@@ -601,7 +672,12 @@ def run_sequential(args, torch, synth, prof, PlacementEngine):
     elapsed = time.perf_counter() - t0
     ks = eng.kernel_stats()          # the last step's k_seq launch, HIP events on the engine's stream
     kn = eng.kernel_names()
-    placements = eng.fetch_placements(len(pods))
+    dump = args.dump_outputs is not None
+    outputs = fetch_outputs(eng, len(pods), cpusets=dump and resvpol,
+                            devices=dump and args.workload == "deviceshare")
+    placements = outputs["placements"]
+    if dump:
+        dump_outputs(args.dump_outputs, outputs)
     seq_s = ks["total_ms"] * 1e-3
     # a DeviceShare batch of device pods among plain ones runs on the pipelined
     # greedy (k_resolve + k_ext_pre / k_ext_final); everything else here in k_seq
@@ -661,7 +737,7 @@ def run_sequential(args, torch, synth, prof, PlacementEngine):
                      "avg_launch_ms": round(seq_s * 1e3, 3),
                      "us_per_pod": round(seq_s * 1e6 / args.pods, 3)},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cb = cpu_baseline(table, pods, cfg, args.cpu_budget, ext=None if resvpol else ext)
         out["cpu_baseline"] = cb
         out["speedup_vs_best_cpu_leg"] = round(value / cb["best_leg"]["pods_per_s"], 1)

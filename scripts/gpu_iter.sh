@@ -4,6 +4,8 @@
 # environment variant in VARIANTS ("X=1" = the defaults).  Time-limited steps;
 # the first failure stops the script.
 set -u
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 mkdir -p gpurun_out
 FILES=${TESTS_FILES:-"tests/test_gpu_parity.py tests/test_gpu_reservation.py tests/test_gpu_numa.py tests/test_fit_kat.py"}
 if [ "${SKIP_TESTS:-0}" != 1 ]; then

@@ -12,6 +12,8 @@
 #           KOORDHIP_PMC_REPLAY: the class lists' and device pods' launches replayed after each call)
 # Every GPU step has its own time limit; the first failure stops the script.
 set -u
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 R=${ROUND:-r04x}
 STAGES=${STAGES:-tests smoke bench stamps prof pmc}
 WORKLOADS=${WORKLOADS:-config4 config3 config5}

@@ -8,6 +8,8 @@
 #   KNOB=V: "X=1" = the defaults
 set -u
 w=$1; knobs=$2; shift 2
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+set -- --full "$@"
 out=gpurun_out/knobs_$w
 mkdir -p $out
 for lib in ${LIBS:-base}; do

@@ -4,6 +4,8 @@
 # Usage: scripts/pmc.sh NAME [bench args...]
 set -u
 name=$1; shift
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+set -- --full "$@"
 export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   mkdir -p gpurun_out/$name/$ctr

@@ -3,6 +3,8 @@
 # per group; <= 8 SQ counters per pass).  Usage: scripts/pmc_sq.sh NAME [bench args...]
 set -u
 name=$1; shift
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+set -- --full "$@"
 export TMPDIR=/tmp
 i=0
 for grp in "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \

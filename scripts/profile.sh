@@ -3,6 +3,8 @@
 # separate pass, see scripts/pmc.sh).  Usage: scripts/profile.sh NAME [bench args...]
 set -u
 name=$1; shift
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+set -- --full "$@"
 export TMPDIR=/tmp
 mkdir -p gpurun_out/$name
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$name -o run \

@@ -7,7 +7,7 @@ set -u
 mkdir -p gpurun_out
 for wl in ${WORKLOADS:-config4 config5}; do
   for w in 1 2 4 8; do
-    KOORDHIP_SHARD_SIM=$w timeout -k 10 300 python bench.py --workload $wl --one-rank-comm --steps ${STEPS:-3} --warmup 1 \
+    KOORDHIP_SHARD_SIM=$w timeout -k 10 300 python bench.py --full --workload $wl --one-rank-comm --steps ${STEPS:-3} --warmup 1 \
       --no-cpu-baseline --no-latency > gpurun_out/shardsim_${wl}_$w.json 2> gpurun_out/shardsim_${wl}_$w.err || { tail -5 gpurun_out/shardsim_${wl}_$w.err; exit 1; }
     python3 - gpurun_out/shardsim_${wl}_$w.json $wl $w <<'PY'
 import json, sys

@@ -4,6 +4,8 @@
 # Usage: CTRS="SQ_WAVES ..." scripts/sqpmc.sh NAME [bench args...]
 set -u
 name=$1; shift
+# the per-kernel figures, the latency leg and the CPU baseline are behind bench.py --full
+set -- --full "$@"
 export TMPDIR=/tmp
 CTRS=${CTRS:-"SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU"}
 mkdir -p gpurun_out/$name
