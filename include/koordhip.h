@@ -39,6 +39,12 @@
  *                              Reserve plugin.go:368-405 over nodeDevice (device_cache.go:44-482) and the
  *                              default allocator (allocator.go:91-122)
  *   static_score columns    <- (upstream) NodeAffinity / TaintToleration Score + NormalizeScore
+ *   koordhip_diagnose / koordhip_fetch_diagnosis / koordhip_fetch_node_status
+ *                           <- the Filter half of a failed cycle: framework.Diagnosis{NodeToStatusMap,
+ *                              UnschedulablePlugins} of the FitError ((upstream) schedule_one.go findNodesThatFitPod),
+ *                              read by frameworkext/eventhandlers/reservation_handler.go:92-94 and handed to every
+ *                              PostFilter (elasticquota/plugin.go:310, reservation/plugin.go:496,
+ *                              coscheduling/core/core.go:289-293)
  *   koordhip_place_stream_ext / koordhip_eval_ext
  *                           <- the exact sequential cycle for profiles with plugins whose scores are normalized
  *                              over the feasible nodes (DefaultNormalizeScore, upstream helper/normalize_score.go)
@@ -52,7 +58,7 @@
 extern "C" {
 #endif
 
-#define KOORDHIP_ABI_VERSION 14
+#define KOORDHIP_ABI_VERSION 15
 
 /* ---- error codes ------------------------------------------------------- */
 #define KOORDHIP_OK 0
@@ -634,6 +640,57 @@ int koordhip_read_pts(koordhip_ctx *ctx, int32_t *cnt);
 /* InterPodAffinity: each count entry's pods per node after the last place
  * call, [ipa_ents][n]. */
 int koordhip_read_ipa(koordhip_ctx *ctx, int32_t *cnt);
+
+/* ---- ABI 15: why a pod is unschedulable ----------------------------------
+ * Per-plugin node counts of a pod's Filter result, reduced on device (136
+ * bytes per pod instead of one status byte per node).  Slot b of `any` and
+ * `first` counts KOORDHIP_ST_* bit (1u << b).
+ *   any[b]   nodes whose status has the bit: every plugin evaluated, no
+ *            short-circuit, exactly koordhip_eval's status
+ *   first[b] nodes whose FIRST failing Filter plugin is the bit, in the
+ *            framework's Filter order STATIC -> FIT -> LA -> NUMA -> RESV: the
+ *            (upstream) default order (NodeUnschedulable / TaintToleration /
+ *            NodeAffinity, then NodeResourcesFit) followed by the koordinator
+ *            plugins as config/manager/scheduler-config.yaml:65-70 lists them.
+ *            The upstream half of that order is k8s v1.24.15's default plugin
+ *            list, which is not vendored: like the other upstream parity in
+ *            DESIGN.md it is restated, unpinned by reference tests.  Upstream
+ *            stops at a node's first failing Filter plugin, so `first` is what
+ *            Diagnosis.UnschedulablePlugins and the "0/N nodes are available"
+ *            event counts are made of.
+ * feasible + sum(first) = n. */
+#define KOORDHIP_DIAG_BITS 16
+typedef struct koordhip_diag {
+  int32_t feasible;                   /* nodes with no Filter bit set */
+  int32_t reserved;
+  int32_t any[KOORDHIP_DIAG_BITS];
+  int32_t first[KOORDHIP_DIAG_BITS];
+} koordhip_diag;
+
+/* Stateless, no commit: out[p] = the record of pods[p] against the current
+ * state.  Every profile koordhip_eval's own kernel covers (Reservation
+ * snapshots included); KOORDHIP_EINVAL on a sequential-cycle profile or
+ * snapshot and for reserve / reservation-operating-mode pods. */
+int koordhip_diagnose(koordhip_ctx *ctx, const koordhip_pod *pods, int32_t n_pods, koordhip_diag *out);
+/* The last place call's unplaced pods at their DECISION state: for every pod
+ * p with out_node[p] < 0 (-1 and -2) the record evaluated on the state the
+ * commits of pods < p left; all-zero records for placed pods.  Computed on
+ * demand from the pods, placements and cpusets the place call left on device
+ * by un-applying later commits from the final rows in registers:
+ * it writes no engine state and costs nothing when not called.
+ * KOORDHIP_ESTATE once a state-changing call followed the place call
+ * (koordhip_commit / koordhip_uncommit and their _ext forms,
+ * koordhip_update_nodes, koordhip_load_snapshot, koordhip_restore, another
+ * stage or place call).  The envelope is koordhip_uncommit's: no Reservation
+ * plugin state, no NUMA topology-policy nodes, no sequential-cycle profile,
+ * no koordhip_pod_ext records, no reserve pods, no communicator attached --
+ * outside it KOORDHIP_EINVAL (the placements are untouched). */
+int koordhip_fetch_diagnosis(koordhip_ctx *ctx, koordhip_diag *out /* [n_pods] */, int32_t n_pods);
+/* The [n] KOORDHIP_ST_* status bytes of ONE unplaced pod of the last place
+ * call at its decision state: the NodeToStatusMap of the pod the host runs
+ * PostFilter (preemption) for.  Same envelope and validity rule;
+ * KOORDHIP_EINVAL for a pod that was placed. */
+int koordhip_fetch_node_status(koordhip_ctx *ctx, int32_t pod_index, uint8_t *status /* [n] */);
 
 /* The same split in two so a caller can time the device part alone: stage
  * (host -> HBM copy) then place (HBM-resident pods, result kept on device

@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-KOORDHIP_ABI_VERSION = 14
+KOORDHIP_ABI_VERSION = 15
 NRES = 5
 NPLUGINS = 4
 
@@ -78,7 +78,7 @@ def numa_policy(required: int = 0, preferred: int = 0, exclusive: int = 0) -> in
 ST_FIT_FAIL, ST_LA_FAIL, ST_NUMA_FAIL, ST_RESV_FAIL, ST_STATIC_FAIL = 1, 2, 4, 8, 16
 ST_DEVICE_FAIL, ST_XFIT_FAIL, ST_PTS_FAIL, ST_IPA_FAIL = 32, 64, 128, 256
 UNSCHEDULABLE, RESERVE_FAILED = -1, -2
-E_INVAL, E_RESERVE = -1, -6
+E_INVAL, E_STATE, E_RESERVE = -1, -3, -6
 UNIQUE_ID_BYTES = 128
 
 _i64p = C.POINTER(C.c_int64)
@@ -226,6 +226,13 @@ POD_DTYPE = np.dtype([
 ], align=True)
 assert POD_DTYPE.itemsize == 96
 TOPK_DTYPE = np.dtype([("node", "<i4"), ("score", "<i4")])
+# numpy twin of koordhip_diag (136 bytes): slot b of any / first counts status bit 1 << b
+DIAG_BITS = 16
+DIAG_DTYPE = np.dtype([("feasible", "<i4"), ("reserved", "<i4"), ("any", "<i4", (DIAG_BITS,)),
+                       ("first", "<i4", (DIAG_BITS,))])
+assert DIAG_DTYPE.itemsize == 136
+# the framework's Filter order behind `first` (include/koordhip.h)
+FILTER_ORDER = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_LA_FAIL, ST_NUMA_FAIL, ST_RESV_FAIL)
 # numpy twin of koordhip_pod_ext (176 bytes)
 POD_EXT_DTYPE = np.dtype([
     ("dev_req", "<i8", (DEV_TYPES, DEV_RES)),
@@ -312,6 +319,9 @@ def load_library(path: str = LIB_PATH):
         "koordhip_commit_ext": (C.c_int, [vp, vp, vp, C.c_int32, _u64p, C.POINTER(C.c_uint32)]),
         "koordhip_uncommit_ext": (C.c_int, [vp, vp, vp, C.c_int32, _u64p, C.POINTER(C.c_uint32)]),
         "koordhip_fetch_cpusets": (C.c_int, [vp, _u64p, C.c_int32]),
+        "koordhip_diagnose": (C.c_int, [vp, vp, C.c_int32, vp]),
+        "koordhip_fetch_diagnosis": (C.c_int, [vp, vp, C.c_int32]),
+        "koordhip_fetch_node_status": (C.c_int, [vp, C.c_int32, _u8p]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -344,6 +354,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_read_devices", "koordhip_read_pts", "koordhip_read_ipa", "koordhip_stage_pods", "koordhip_stage_pods_ext", "koordhip_place_staged", "koordhip_fetch_placements",
     "koordhip_synchronize", "koordhip_checkpoint", "koordhip_restore", "koordhip_commit", "koordhip_uncommit",
     "koordhip_commit_ext", "koordhip_uncommit_ext",
+    "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

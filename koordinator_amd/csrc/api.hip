@@ -20,6 +20,7 @@
 
 #include "../../include/koordhip.h"
 #include "cls.h"
+#include "diag.h"
 #include "kernels.h"
 #include "seq.h"
 
@@ -255,6 +256,13 @@ struct koordhip_ctx {
   int64_t last_exec = 0, last_ext_exec = 0;
   const uint32_t *last_evc = nullptr, *last_reev = nullptr;
   int32_t last_plan_us = 0;  // the class-list plan of the staged batch (0: none made)
+  // unschedulable-pod diagnosis (diag.hip)
+  bool diag_valid = false;         // a place call ran and no state-changing call followed: its pods, placements and
+                                   // cpusets on device still describe how the current state came about
+  void *d_diag_ws = nullptr;       // the replay's lists (kh::diag_ws_ints)
+  void *d_diag_rec = nullptr;      // records / one pod's status bytes
+  void *d_diag_pods = nullptr;     // koordhip_diagnose's pods
+  size_t diag_ws_cap = 0, diag_rec_cap = 0, diag_pods_cap = 0;
 };
 
 namespace {
@@ -1274,7 +1282,8 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_etk_pcnt[1], (void *)c->d_etk_sync[0], (void *)c->d_etk_sync[1], c->d_upd,
                   (void *)c->d_podx, (void *)c->d_devout, (void *)c->d_seqg, c->d_seqdesc, (void *)c->d_pod_cls,
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
-                  (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr})
+                  (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
+                  c->d_diag_rec, c->d_diag_pods})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
     if (c->ev_res[i]) (void)hipEventDestroy(c->ev_res[i]);
@@ -1316,6 +1325,7 @@ int koordhip_load_snapshot(koordhip_ctx *c, const koordhip_node_soa *s, int32_t 
   if (int e = validate_soa(s)) return e;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->diag_valid = false;
   free_cols(c);
   for (void *p : c->ckpt) (void)hipFree(p);
   c->ckpt.clear();
@@ -1416,6 +1426,7 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
   if (!c || !idx) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (m <= 0) return 0;
+  c->diag_valid = false;
   if (int e = validate_soa(rows)) return e;
   // ---- validate everything before the first device write: a rejected call
   //      leaves the snapshot untouched
@@ -2068,6 +2079,7 @@ static int stage_pods_impl(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_
   std::vector<kh::DevPod> hp;
   if (int e = to_dev_pods(pods, n_pods, hp, ext, devshare_resv_on(c))) return e;
   HIP_TRY(hipSetDevice(c->device));
+  c->diag_valid = false;  // the last place call's pods are overwritten
   if (n_pods > c->pods_cap) {
     if (c->d_pods) HIP_TRY(hipFree(c->d_pods));
     if (c->d_out) HIP_TRY(hipFree(c->d_out));
@@ -2476,7 +2488,9 @@ int koordhip_place_staged(koordhip_ctx *c) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
   if (c->n_staged > 0 && c->staged_dsr != devshare_resv_on(c))
     return fail(KOORDHIP_ESTATE, "the pods were staged under a snapshot with(out) reservations; stage them again");
+  c->diag_valid = false;
   int e = place_staged_impl(c);
+  c->diag_valid = !e;
   if (e && c->group) c->group->abort();
   if (!e && std::getenv("KOORDHIP_PMC_REPLAY") && std::getenv("KOORDHIP_SERIAL")) e = pmc_replay(c);
   return e;
@@ -3493,6 +3507,7 @@ int koordhip_restore(koordhip_ctx *c) {
   auto cols = mutable_cols(c);
   if (c->ckpt.size() != cols.size()) return fail(KOORDHIP_ESTATE, "no checkpoint");
   HIP_TRY(hipSetDevice(c->device));
+  c->diag_valid = false;
   for (size_t i = 0; i < cols.size(); i++)
     if (cols[i].second) HIP_TRY(hipMemcpyAsync(cols[i].first, c->ckpt[i], cols[i].second, hipMemcpyDeviceToDevice, c->stream));
   return 0;
@@ -3521,6 +3536,7 @@ static int commit_impl(koordhip_ctx *c, const koordhip_pod *pod, int32_t node, i
   uint64_t *d_cpus = reinterpret_cast<uint64_t *>(reinterpret_cast<char *>(c->d_rc) + sizeof(uint64_t));
   std::vector<kh::DevPod> hp;
   if (int e = to_dev_pods(pod, 1, hp)) return e;
+  c->diag_valid = false;
   HIP_TRY(hipMemcpyAsync(c->d_tmp_pod, hp.data(), sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
   if (sign < 0 && cpus_io)
     HIP_TRY(hipMemcpyAsync(d_cpus, cpus_io, KOORDHIP_NUMA_WORDS * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
@@ -3568,6 +3584,7 @@ static int commit_ext_impl(koordhip_ctx *c, const koordhip_pod *pod, const koord
   uint32_t *d_dev = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(c->d_rc) + 40);
   std::vector<kh::DevPod> hp;
   if (int e = to_dev_pods(pod, 1, hp, ext, devshare_resv_on(c))) return e;
+  c->diag_valid = false;
   HIP_TRY(hipMemcpyAsync(c->d_tmp_pod, hp.data(), sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(hipMemcpyAsync(c->d_tmp_podx, ext, sizeof(kh::DevPodX), hipMemcpyHostToDevice, c->stream));
   uint64_t cz[KOORDHIP_NUMA_WORDS] = {0, 0, 0, 0};
@@ -3606,6 +3623,114 @@ int koordhip_uncommit_ext(koordhip_ctx *c, const koordhip_pod *pod, const koordh
 }
 int koordhip_uncommit(koordhip_ctx *c, const koordhip_pod *pod, int32_t node, const uint64_t *cpus) {
   return commit_impl(c, pod, node, -1, const_cast<uint64_t *>(cpus));
+}
+
+// ---- unschedulable-pod diagnosis (diag.hip) --------------------------------
+
+int koordhip_diagnose(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_pods, koordhip_diag *out) {
+  static_assert(sizeof(koordhip_diag) == 136, "koordhip_diag is 34 int32 counters");
+  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
+  if (n_pods == 0) return 0;
+  bool reserve = false;
+  if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
+  if (c->seq)
+    return fail(KOORDHIP_EINVAL, "koordhip_diagnose: the profile / snapshot evaluates in the sequential cycle "
+                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
+  if (reserve) return fail(KOORDHIP_EINVAL, "koordhip_diagnose: reserve / reservation-operating-mode pods are not covered");
+  std::vector<kh::DevPod> hp;
+  if (int e = to_dev_pods(pods, n_pods, hp)) return e;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t rb = (size_t)n_pods * sizeof(koordhip_diag);
+  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, (size_t)n_pods * sizeof(kh::DevPod))) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), (size_t)n_pods * sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  HIP_TRY(kh::launch_diag(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods), n_pods,
+                          static_cast<int32_t *>(c->d_diag_rec), c->stream));
+  HIP_TRY(hipMemcpyAsync(out, c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The checks koordhip_fetch_diagnosis and koordhip_fetch_node_status share:
+// the last place call drained, nothing changed the state since, and the call
+// lies in the envelope where every commit of the stream is invertible from
+// what the engine keeps (koordhip_uncommit's).
+static int diag_replay_ready(koordhip_ctx *c) {
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int e = pipe_status(c)) return e;
+  if (!c->diag_valid)
+    return fail(KOORDHIP_ESTATE, "no place call to diagnose: none ran, or a state-changing call (commit / uncommit, "
+                                 "update_nodes, load_snapshot, restore, stage) followed it");
+  if (c->seq || c->seq_profile || c->last_seq)
+    return fail(KOORDHIP_EINVAL, "decision-state diagnosis: sequential-cycle profiles are not covered");
+  if (c->dc.resv)
+    return fail(KOORDHIP_EINVAL, "decision-state diagnosis: not with Reservation plugin state (whether a Reserve took a "
+                                 "reservation is not kept)");
+  if (c->dc.zones)
+    return fail(KOORDHIP_EINVAL, "decision-state diagnosis: not with NUMA topology-policy nodes (a Reserve's zone amounts "
+                                 "are not kept)");
+  if (c->podx_staged || c->staged_ext || c->staged_reserve)
+    return fail(KOORDHIP_EINVAL, "decision-state diagnosis: not for streams with koordhip_pod_ext records or reserve pods");
+  if (c->comm || c->group || c->world > 1)
+    return fail(KOORDHIP_EINVAL, "decision-state diagnosis: not with a communicator attached");
+  return 0;
+}
+
+int koordhip_fetch_diagnosis(koordhip_ctx *c, koordhip_diag *out, int32_t n_pods) {
+  if (!c || (!out && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
+  if (int e = diag_replay_ready(c)) return e;
+  if (n_pods > c->n_staged) return fail(KOORDHIP_EINVAL, "n_pods exceeds the staged stream");
+  if (n_pods == 0) return 0;
+  // the lists cover the whole stream: the commits of pods >= n_pods are un-applied too
+  const int32_t P = c->n_staged, n = c->n;
+  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
+  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
+  const kh::DiagLists l = kh::diag_lists(ws, n, P);
+  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
+  int32_t U = 0;
+  HIP_TRY(hipMemcpyAsync(&U, l.tot + 1, sizeof(U), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_diag));
+  if (U <= 0) return 0;
+  const size_t rb = (size_t)U * sizeof(koordhip_diag);
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, l, U, -1, static_cast<int32_t *>(c->d_diag_rec),
+                                 nullptr, c->stream));
+  std::vector<koordhip_diag> rec((size_t)U);
+  std::vector<int32_t> ul((size_t)U);
+  HIP_TRY(hipMemcpyAsync(rec.data(), c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(ul.data(), l.ul, (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int32_t k = 0; k < U; k++)
+    if (ul[k] >= 0 && ul[k] < n_pods) out[ul[k]] = rec[k];
+  return 0;
+}
+
+int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *status) {
+  if (!c || !status) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (int e = diag_replay_ready(c)) return e;
+  if (pod_index < 0 || pod_index >= c->n_staged) return fail(KOORDHIP_EINVAL, "pod_index outside the staged stream");
+  int32_t node = 0;
+  HIP_TRY(hipMemcpy(&node, c->d_out + pod_index, sizeof(node), hipMemcpyDeviceToHost));
+  if (node >= 0) return fail(KOORDHIP_EINVAL, "the pod was placed: it has no unschedulable status");
+  const int32_t P = c->n_staged, n = c->n;
+  if (n == 0) return 0;
+  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, (size_t)n)) return e;
+  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
+  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
+  HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
+                                 static_cast<uint8_t *>(c->d_diag_rec), c->stream));
+  HIP_TRY(hipMemcpyAsync(status, c->d_diag_rec, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 int koordhip_last_stats(koordhip_ctx *c, double *eval_ms, int64_t *eval_launches, int64_t *evals, double *total_ms) {

@@ -177,19 +177,7 @@ __global__ void k_eval_full(DevCfg c, DevNodes d, const DevPod *__restrict__ pod
     // a topology-policy node's zone row shares the reserved CPUs' bytes: read it again
     if (c.zones && topo_policy(nr.nflags) != 0) load_zones(nr, d, i);
   }
-  if (status) {
-    uint8_t b = 0;
-    if ((c.filt & KOORDHIP_PLUGIN_NODE_STATIC) && !((v.sa >> pod.sclass) & 1u)) b |= KOORDHIP_ST_STATIC_FAIL;
-    if ((c.filt & KOORDHIP_PLUGIN_FIT) && !fit_filter(pod, v)) b |= KOORDHIP_ST_FIT_FAIL;
-    if ((c.filt & KOORDHIP_PLUGIN_LOADAWARE) && !la_filter(pod, v)) b |= KOORDHIP_ST_LA_FAIL;
-    if ((c.filt & KOORDHIP_PLUGIN_NUMA) &&
-        (!numa_filter<true>(pod, nr, d.nu.cls) || (c.amp && !amp_filter_ok(pod, v, nr))))
-      b |= KOORDHIP_ST_NUMA_FAIL;
-    if ((c.filt & KOORDHIP_PLUGIN_RESERVATION) &&
-        (nmatch > 0 ? !resv_filter(pod, v, nr, mm, nmatch) : (pod.flags & KOORDHIP_POD_RESV_AFFINITY) != 0))
-      b |= KOORDHIP_ST_RESV_FAIL;
-    status[(size_t)p * d.n + i] = b;
-  }
+  if (status) status[(size_t)p * d.n + i] = (uint8_t)filter_status(c, pod, v, nr, d.nu.cls, nmatch, mm);
   if (scores) {
     int32_t *row = scores + (size_t)p * KOORDHIP_NPLUGINS * d.n;
     row[i] = (c.score & KOORDHIP_PLUGIN_FIT) ? fit_score(pod, v, c) : 0;

@@ -248,6 +248,29 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_fetch_cpusets(self._ctx, abi.ptr(out, C.c_uint64), n))
         return out
 
+    # ---- why a pod is unschedulable (koordinator_amd.diagnosis reads the records)
+    def diagnose(self, pods: np.ndarray) -> np.ndarray:
+        """Per-plugin node counts (abi.DIAG_DTYPE records) of `pods` against the
+        current state; stateless, no commit."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        out = np.zeros(len(pods), abi.DIAG_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_diagnose(self._ctx, pods.ctypes.data, len(pods), out.ctypes.data))
+        return out
+
+    def fetch_diagnosis(self, n: int) -> np.ndarray:
+        """The records of the last place call's unplaced pods (out_node < 0) at
+        the state each was decided on; all-zero records for placed pods."""
+        out = np.zeros(n, abi.DIAG_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_fetch_diagnosis(self._ctx, out.ctypes.data, n))
+        return out
+
+    def fetch_node_status(self, pod_index: int) -> np.ndarray:
+        """[n] abi.ST_* status bytes of one unplaced pod of the last place call
+        at its decision state (the PostFilter NodeToStatusMap)."""
+        out = np.zeros(self.n, np.uint8)
+        abi.check(self.lib, self.lib.koordhip_fetch_node_status(self._ctx, int(pod_index), abi.ptr(out, C.c_uint8)))
+        return out
+
     def last_stats(self) -> dict:
         em, tm = C.c_double(), C.c_double()
         nl, ne = C.c_int64(), C.c_int64()
