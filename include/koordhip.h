@@ -692,6 +692,95 @@ int koordhip_fetch_diagnosis(koordhip_ctx *ctx, koordhip_diag *out /* [n_pods] *
  * KOORDHIP_EINVAL for a pod that was placed. */
 int koordhip_fetch_node_status(koordhip_ctx *ctx, int32_t pod_index, uint8_t *status /* [n] */);
 
+/* ---- preemption dry run (additive to ABI 15: detect it by the symbols) -----
+ * The PostFilter of elasticquota/plugin.go:310-329: SelectVictimsOnNode
+ * (elasticquota/preempt.go:111-215) on EVERY node, then one candidate picked,
+ * all on device against the current engine state.  It writes no engine state.
+ *
+ * The host keeps a table of the pods that sit on the nodes: one record per
+ * assigned pod.  `pod` is the record its Reserve used, i.e. what
+ * NodeInfo.RemovePod / AddPod move. */
+#define KOORDHIP_PREEMPT_QRES 4        /* quota dimensions (the host chooses which resources) */
+#define KOORDHIP_PREEMPT_PDBS 8        /* PodDisruptionBudgets of one table */
+#define KOORDHIP_PREEMPT_NODE_PODS 128 /* listed pods per node at most */
+
+#define KOORDHIP_ASG_NONPREEMPTIBLE 1u /* extension.IsPodNonPreemptible */
+#define KOORDHIP_ASG_IN_QUOTA 2u       /* quotaInfo.IsPodExist: the quota's used moves with the pod (plugin.go:302-305) */
+
+typedef struct koordhip_assigned {
+  koordhip_pod pod;
+  int32_t node;       /* node index in the loaded snapshot */
+  int32_t priority;   /* corev1helpers.PodPriority */
+  int64_t start_time; /* GetPodStartTime as unix ns (status.startTime, else the host's "now") */
+  int32_t quota;      /* id of getPodAssociateQuotaName, host-assigned, >= 0 */
+  uint32_t flags;     /* KOORDHIP_ASG_* */
+  uint32_t pdb_mask;  /* bit i: PDB i matches the pod and the pod is not in its DisruptedPods (preempt.go:231-250) */
+  uint32_t reserved;
+  int64_t qreq[KOORDHIP_PREEMPT_QRES]; /* core.PodRequestsAndLimits in the quota dimensions, 0 .. 2^53 */
+} koordhip_assigned;
+
+typedef struct koordhip_preemptor {
+  koordhip_pod pod;
+  int32_t priority;
+  int32_t quota;      /* -1: postFilterState.skip (no quota check; canPreempt still compares ids: no victims) */
+  int64_t q_used[KOORDHIP_PREEMPT_QRES];    /* postFilterState.used, 0 .. 2^53 */
+  int64_t q_runtime[KOORDHIP_PREEMPT_QRES]; /* postFilterState.runtime */
+  int64_t q_req[KOORDHIP_PREEMPT_QRES];     /* the preemptor's own request, 0 .. 2^53 */
+  uint32_t q_mask;    /* dimensions present in runtime (quotav1.LessThanOrEqual walks runtime's keys only) */
+  uint32_t reserved;
+} koordhip_preemptor;
+
+#define KOORDHIP_PREEMPT_CANDIDATE 0    /* the preemptor fits once the victims are gone */
+#define KOORDHIP_PREEMPT_NO_VICTIMS 1   /* no pod canPreempt accepts (preempt.go:150-153) */
+#define KOORDHIP_PREEMPT_UNFIT 2        /* does not fit with every potential victim removed (:161-163) */
+#define KOORDHIP_PREEMPT_ERROR 3        /* a pod removed twice: NodeInfo.RemovePod fails, the node is dropped */
+#define KOORDHIP_PREEMPT_UNRESOLVABLE 4 /* KOORDHIP_ST_STATIC_FAIL: skipped by nodesWherePreemptionMightHelp */
+#define KOORDHIP_PREEMPT_STATUSES 5
+
+/* One node's verdict for one preemptor.  Every field but status is 0 unless
+ * status is CANDIDATE (and 0 for a candidate without victims). */
+typedef struct koordhip_preempt_node {
+  int32_t status;
+  int32_t n_victims;        /* the victims list's length */
+  int32_t n_pdb_violations; /* PDB-violating pods that did not fit back (:201-207) */
+  int32_t top_priority;     /* priority of the list's first victim (upstream reads Pods[0]) */
+  int64_t sum_priority;     /* sum of (priority + 2^31) */
+  int64_t earliest_start;   /* smallest start_time among the victims of maximal priority */
+} koordhip_preempt_node;
+
+typedef struct koordhip_preempt_result {
+  int32_t node;                            /* the chosen node, -1: no candidate */
+  int32_t count[KOORDHIP_PREEMPT_STATUSES]; /* nodes per status */
+  koordhip_preempt_node best;              /* the chosen node's verdict (zero when node = -1) */
+} koordhip_preempt_result;
+
+/* Upload the table and build each node's list on device, ordered by
+ * util.MoreImportantPod (priority descending, start_time ascending) and then
+ * by ascending input index (Go's sort.Slice is unstable there; this rule is
+ * the engine's).  The table does not depend on the node state: it stays until
+ * the next call of this function or of load_snapshot.  KOORDHIP_EINVAL for a
+ * node outside [0, n), more than KOORDHIP_PREEMPT_NODE_PODS pods on a node,
+ * n_pdb above KOORDHIP_PREEMPT_PDBS, a pdb_mask bit at or above n_pdb. */
+int koordhip_preempt_load_pods(koordhip_ctx *ctx, const koordhip_assigned *a, int32_t n_assigned,
+                               const int32_t *pdb_allowed /* [n_pdb] DisruptionsAllowed */, int32_t n_pdb);
+/* The dry run of n_pre preemptors, each on its own against the current state.
+ * out[p].node is the lexicographic minimum over the CANDIDATE nodes of (has
+ * victims, n_pdb_violations, top_priority, sum_priority, n_victims,
+ * -earliest_start, node index): upstream v1.24 pickOneNodeForPreemption with
+ * the lowest node index as its last rule.  victims (may be NULL) receives the
+ * chosen node's victims as indices into a[], in the order the reference
+ * appends them, padded with -1; with max_victims below best.n_victims the
+ * list is truncated.  Profiles whose Filter is NodeResourcesFit, LoadAware
+ * and the static filters on the pipelined path; KOORDHIP_EINVAL for
+ * NodeNUMAResource or Reservation in the Filter, Reservation snapshots,
+ * sequential-cycle profiles, reserve pods and an attached communicator;
+ * KOORDHIP_ESTATE without a snapshot or a loaded table. */
+int koordhip_preempt(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                     int32_t *victims /* [n_pre][max_victims] */, int32_t max_victims);
+/* One preemptor's verdict on every node (the evaluator's per-node statuses). */
+int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *pre,
+                                   koordhip_preempt_node *per_node /* [n] */);
+
 /* The same split in two so a caller can time the device part alone: stage
  * (host -> HBM copy) then place (HBM-resident pods, result kept on device
  * until koordhip_fetch_placements). */

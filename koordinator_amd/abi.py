@@ -233,6 +233,28 @@ DIAG_DTYPE = np.dtype([("feasible", "<i4"), ("reserved", "<i4"), ("any", "<i4", 
 assert DIAG_DTYPE.itemsize == 136
 # the framework's Filter order behind `first` (include/koordhip.h)
 FILTER_ORDER = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_LA_FAIL, ST_NUMA_FAIL, ST_RESV_FAIL)
+# the preemption dry run (koordhip_preempt*): numpy twins of koordhip_assigned (160 bytes),
+# koordhip_preemptor (208), koordhip_preempt_node (32) and koordhip_preempt_result (56)
+PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
+ASG_NONPREEMPTIBLE, ASG_IN_QUOTA = 1, 2
+PREEMPT_CANDIDATE, PREEMPT_NO_VICTIMS, PREEMPT_UNFIT, PREEMPT_ERROR, PREEMPT_UNRESOLVABLE = range(5)
+PREEMPT_STATUSES = 5
+ASSIGNED_DTYPE = np.dtype([
+    ("pod", POD_DTYPE), ("node", "<i4"), ("priority", "<i4"), ("start_time", "<i8"), ("quota", "<i4"),
+    ("flags", "<u4"), ("pdb_mask", "<u4"), ("reserved", "<u4"), ("qreq", "<i8", (PREEMPT_QRES,)),
+], align=True)
+PREEMPTOR_DTYPE = np.dtype([
+    ("pod", POD_DTYPE), ("priority", "<i4"), ("quota", "<i4"), ("q_used", "<i8", (PREEMPT_QRES,)),
+    ("q_runtime", "<i8", (PREEMPT_QRES,)), ("q_req", "<i8", (PREEMPT_QRES,)), ("q_mask", "<u4"), ("reserved", "<u4"),
+], align=True)
+PREEMPT_NODE_DTYPE = np.dtype([
+    ("status", "<i4"), ("n_victims", "<i4"), ("n_pdb_violations", "<i4"), ("top_priority", "<i4"),
+    ("sum_priority", "<i8"), ("earliest_start", "<i8"),
+], align=True)
+PREEMPT_RESULT_DTYPE = np.dtype([("node", "<i4"), ("count", "<i4", (PREEMPT_STATUSES,)), ("best", PREEMPT_NODE_DTYPE)],
+                                align=True)
+assert (ASSIGNED_DTYPE.itemsize, PREEMPTOR_DTYPE.itemsize, PREEMPT_NODE_DTYPE.itemsize,
+        PREEMPT_RESULT_DTYPE.itemsize) == (160, 208, 32, 56)
 # numpy twin of koordhip_pod_ext (176 bytes)
 POD_EXT_DTYPE = np.dtype([
     ("dev_req", "<i8", (DEV_TYPES, DEV_RES)),
@@ -322,6 +344,9 @@ def load_library(path: str = LIB_PATH):
         "koordhip_diagnose": (C.c_int, [vp, vp, C.c_int32, vp]),
         "koordhip_fetch_diagnosis": (C.c_int, [vp, vp, C.c_int32]),
         "koordhip_fetch_node_status": (C.c_int, [vp, C.c_int32, _u8p]),
+        "koordhip_preempt_load_pods": (C.c_int, [vp, vp, C.c_int32, _i32p, C.c_int32]),
+        "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
+        "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -355,6 +380,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_synchronize", "koordhip_checkpoint", "koordhip_restore", "koordhip_commit", "koordhip_uncommit",
     "koordhip_commit_ext", "koordhip_uncommit_ext",
     "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
+    "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

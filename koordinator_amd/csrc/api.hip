@@ -21,6 +21,7 @@
 #include "../../include/koordhip.h"
 #include "cls.h"
 #include "diag.h"
+#include "preempt.h"
 #include "kernels.h"
 #include "seq.h"
 
@@ -263,6 +264,16 @@ struct koordhip_ctx {
   void *d_diag_rec = nullptr;      // records / one pod's status bytes
   void *d_diag_pods = nullptr;     // koordhip_diagnose's pods
   size_t diag_ws_cap = 0, diag_rec_cap = 0, diag_pods_cap = 0;
+  // preemption dry run (preempt.hip)
+  bool pre_loaded = false;         // koordhip_preempt_load_pods ran on this snapshot
+  int32_t pre_m = 0;               // its assigned pods
+  kh::PdbAllowed pre_pdb{};        // DisruptionsAllowed (0 past n_pdb: no mask bit reaches there)
+  void *d_pre_raw = nullptr;       // the table in input order
+  void *d_pre_tab = nullptr;       // ... permuted into the nodes' lists
+  void *d_pre_ws = nullptr;        // the lists' workspace (kh::preempt_ws_ints; off lives here)
+  void *d_pre_in = nullptr;        // the preemptors
+  void *d_pre_out = nullptr;       // counts, partials, results, victims / the per-node verdicts
+  size_t pre_raw_cap = 0, pre_tab_cap = 0, pre_ws_cap = 0, pre_in_cap = 0, pre_out_cap = 0;
 };
 
 namespace {
@@ -1283,7 +1294,7 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_podx, (void *)c->d_devout, (void *)c->d_seqg, c->d_seqdesc, (void *)c->d_pod_cls,
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
                   (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
-                  c->d_diag_rec, c->d_diag_pods})
+                  c->d_diag_rec, c->d_diag_pods, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
     if (c->ev_res[i]) (void)hipEventDestroy(c->ev_res[i]);
@@ -1326,6 +1337,7 @@ int koordhip_load_snapshot(koordhip_ctx *c, const koordhip_node_soa *s, int32_t 
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->diag_valid = false;
+  c->pre_loaded = false;
   free_cols(c);
   for (void *p : c->ckpt) (void)hipFree(p);
   c->ckpt.clear();
@@ -3729,6 +3741,186 @@ int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *stat
   HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
                                  static_cast<uint8_t *>(c->d_diag_rec), c->stream));
   HIP_TRY(hipMemcpyAsync(status, c->d_diag_rec, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- preemption dry run (preempt.hip) --------------------------------------
+
+constexpr int64_t kQuotaLimit = 1ll << 53;  // quota amounts: sums of 128 of them and one more stay far inside int64
+
+int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int32_t n_assigned, const int32_t *pdb_allowed,
+                               int32_t n_pdb) {
+  static_assert(sizeof(koordhip_assigned) == 160 && sizeof(koordhip_preemptor) == 208 &&
+                    sizeof(koordhip_preempt_node) == 32 && sizeof(koordhip_preempt_result) == 56,
+                "preemption records");
+  if (!c || (!a && n_assigned > 0) || (!pdb_allowed && n_pdb > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  if (n_assigned < 0 || n_pdb < 0) return fail(KOORDHIP_EINVAL, "n_assigned / n_pdb < 0");
+  if (n_pdb > KOORDHIP_PREEMPT_PDBS)
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: more than KOORDHIP_PREEMPT_PDBS (8) PodDisruptionBudgets");
+  c->pre_loaded = false;
+  const int32_t n = c->n, m = n_assigned;
+  std::vector<kh::DevPod> hp;
+  std::vector<koordhip_pod> pods((size_t)m);
+  for (int32_t j = 0; j < m; j++) pods[j] = a[j].pod;
+  if (int e = to_dev_pods(pods.data(), m, hp)) return e;
+  std::vector<kh::DevAsg> raw((size_t)m);
+  std::vector<int32_t> per((size_t)n, 0);
+  for (int32_t j = 0; j < m; j++) {
+    const koordhip_assigned &s = a[j];
+    if (s.node < 0 || s.node >= n)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: assigned pod " + std::to_string(j) + " names node " +
+                                       std::to_string(s.node) + " outside the snapshot");
+    if (++per[s.node] > KOORDHIP_PREEMPT_NODE_PODS)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: more than KOORDHIP_PREEMPT_NODE_PODS (128) pods on node " +
+                                       std::to_string(s.node));
+    if (n_pdb < 32 && (s.pdb_mask >> n_pdb) != 0u)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: assigned pod " + std::to_string(j) +
+                                       " has a pdb_mask bit at or above n_pdb");
+    if (s.quota < 0) return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: an assigned pod's quota id is >= 0");
+    if (s.flags & ~(KOORDHIP_ASG_NONPREEMPTIBLE | KOORDHIP_ASG_IN_QUOTA))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: unknown koordhip_assigned.flags bit");
+    kh::DevAsg &o = raw[j];
+    std::memset(&o, 0, sizeof(o));
+    o.pod = hp[j];
+    o.start = s.start_time;
+    for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++) {
+      if (s.qreq[r] < 0 || s.qreq[r] > kQuotaLimit)
+        return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: qreq outside [0, 2^53]");
+      o.qreq[r] = s.qreq[r];
+    }
+    o.prio = s.priority;
+    o.quota = s.quota;
+    o.flags = s.flags;
+    o.pdb_mask = s.pdb_mask;
+    o.idx = j;
+    o.node = s.node;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t tb = (size_t)m * sizeof(kh::DevAsg);
+  if (int e = ensure(c, &c->d_pre_raw, &c->pre_raw_cap, tb)) return e;
+  if (int e = ensure(c, &c->d_pre_tab, &c->pre_tab_cap, tb)) return e;
+  if (int e = ensure(c, &c->d_pre_ws, &c->pre_ws_cap, kh::preempt_ws_ints(n, m) * sizeof(int32_t))) return e;
+  if (m > 0) HIP_TRY(hipMemcpyAsync(c->d_pre_raw, raw.data(), tb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(kh::launch_preempt_lists(static_cast<const kh::DevAsg *>(c->d_pre_raw), static_cast<kh::DevAsg *>(c->d_pre_tab),
+                                   m, n, static_cast<int32_t *>(c->d_pre_ws), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // raw is the host's
+  c->pre_pdb = kh::PdbAllowed{};
+  for (int32_t b = 0; b < n_pdb; b++) c->pre_pdb.a[b] = pdb_allowed[b];
+  c->pre_m = m;
+  c->pre_loaded = true;
+  return 0;
+}
+
+// The checks the two dry-run calls share, and the preemptors' upload.
+static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre) {
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  if (!c->pre_loaded)
+    return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
+                                 "load_snapshot)");
+  if (c->seq || c->seq_profile)
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt: the profile / snapshot evaluates in the sequential cycle "
+                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
+  if (c->dc.filt & KOORDHIP_PLUGIN_NUMA)
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with NodeNUMAResource in the Filter (it has no "
+                                 "PreFilterExtensions: its state does not move in a dry run)");
+  if (c->dc.resv || (c->dc.filt & KOORDHIP_PLUGIN_RESERVATION))
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
+                                 "not kept)");
+  if (c->comm || c->group || c->world > 1) return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with a communicator attached");
+  std::vector<koordhip_pod> pods((size_t)n_pre);
+  for (int32_t p = 0; p < n_pre; p++) {
+    pods[p] = pre[p].pod;
+    if (pods[p].flags & (KOORDHIP_POD_RESERVE | KOORDHIP_POD_RESV_OPERATING))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: reserve / reservation-operating-mode pods are not covered");
+    if (pre[p].quota < -1) return fail(KOORDHIP_EINVAL, "koordhip_preempt: quota is an id >= 0, or -1 (skip)");
+    if (pre[p].q_mask >> KOORDHIP_PREEMPT_QRES) return fail(KOORDHIP_EINVAL, "koordhip_preempt: q_mask bit past the quota dimensions");
+    for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++)
+      if (pre[p].q_used[r] < 0 || pre[p].q_used[r] > kQuotaLimit || pre[p].q_req[r] < 0 || pre[p].q_req[r] > kQuotaLimit)
+        return fail(KOORDHIP_EINVAL, "koordhip_preempt: q_used / q_req outside [0, 2^53]");
+  }
+  std::vector<kh::DevPod> hp;
+  if (int e = to_dev_pods(pods.data(), n_pre, hp)) return e;
+  std::vector<kh::DevPre> dp((size_t)n_pre);
+  for (int32_t p = 0; p < n_pre; p++) {
+    kh::DevPre &o = dp[p];
+    std::memset(&o, 0, sizeof(o));
+    o.pod = hp[p];
+    for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++) {
+      o.used[r] = pre[p].q_used[r];
+      o.runtime[r] = pre[p].q_runtime[r];
+      o.req[r] = pre[p].q_req[r];
+    }
+    o.prio = pre[p].priority;
+    o.quota = pre[p].quota;
+    o.qmask = pre[p].q_mask;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t pb = (size_t)n_pre * sizeof(kh::DevPre);
+  if (int e = ensure(c, &c->d_pre_in, &c->pre_in_cap, pb)) return e;
+  HIP_TRY(hipMemcpyAsync(c->d_pre_in, dp.data(), pb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // dp is this function's
+  return 0;
+}
+
+int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                     int32_t *victims, int32_t max_victims) {
+  if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
+  if (int e = preempt_ready(c, pre, n_pre)) return e;
+  if (n_pre == 0) return 0;
+  const int32_t n = c->n;
+  const size_t nv = victims ? (size_t)n_pre * max_victims : 0;
+  if (n == 0) {
+    std::memset(out, 0, (size_t)n_pre * sizeof(*out));
+    for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
+    for (size_t k = 0; k < nv; k++) victims[k] = -1;
+    return 0;
+  }
+  const size_t nb = (size_t)kh::preempt_blocks(n);
+  const size_t cb = ((size_t)n_pre * KOORDHIP_PREEMPT_STATUSES * sizeof(int32_t) + 7) & ~(size_t)7;
+  const size_t pb = (size_t)n_pre * nb * sizeof(kh::PreemptPartial);
+  const size_t rb = (size_t)n_pre * sizeof(koordhip_preempt_result);
+  const size_t vb = nv * sizeof(int32_t);
+  if (int e = ensure(c, &c->d_pre_out, &c->pre_out_cap, cb + pb + rb + vb)) return e;
+  char *base = static_cast<char *>(c->d_pre_out);
+  int32_t *d_cnt = reinterpret_cast<int32_t *>(base);
+  kh::PreemptPartial *d_part = reinterpret_cast<kh::PreemptPartial *>(base + cb);
+  koordhip_preempt_result *d_res = reinterpret_cast<koordhip_preempt_result *>(base + cb + pb);
+  int32_t *d_vic = nv ? reinterpret_cast<int32_t *>(base + cb + pb + rb) : nullptr;
+  const kh::DevAsg *tab = static_cast<const kh::DevAsg *>(c->d_pre_tab);
+  const int32_t *off = kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n);
+  const kh::DevPre *dp = static_cast<const kh::DevPre *>(c->d_pre_in);
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, cb, c->stream));
+  if (nv) HIP_TRY(hipMemsetAsync(d_vic, 0xFF, vb, c->stream));
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, c->stream));
+  HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, d_res, d_vic, max_victims,
+                                  c->stream));
+  HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
+  if (nv) HIP_TRY(hipMemcpyAsync(victims, d_vic, vb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pre, koordhip_preempt_node *per_node) {
+  if (!c || !pre || !per_node) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (int e = preempt_ready(c, pre, 1)) return e;
+  const int32_t n = c->n;
+  if (n == 0) return 0;
+  const size_t nb = (size_t)kh::preempt_blocks(n);
+  const size_t cb = 8 * sizeof(int32_t);
+  const size_t pb = nb * sizeof(kh::PreemptPartial);
+  const size_t vb = (size_t)n * sizeof(koordhip_preempt_node);
+  if (int e = ensure(c, &c->d_pre_out, &c->pre_out_cap, cb + pb + vb)) return e;
+  char *base = static_cast<char *>(c->d_pre_out);
+  koordhip_preempt_node *d_ver = reinterpret_cast<koordhip_preempt_node *>(base + cb + pb);
+  HIP_TRY(hipMemsetAsync(base, 0, cb, c->stream));
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
+                             kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
+                             static_cast<const kh::DevPre *>(c->d_pre_in), 1, reinterpret_cast<int32_t *>(base),
+                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, c->stream));
+  HIP_TRY(hipMemcpyAsync(per_node, d_ver, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -25,6 +25,9 @@ size_t diag_ws_ints(int32_t n, int32_t P);
 DiagLists diag_lists(int32_t *ws, int32_t n, int32_t P);
 hipError_t launch_diag_lists(int32_t *ws, const int32_t *out_node, int32_t P, int32_t n, hipStream_t s);
 
+// k_diag_scan on its own (preempt.hip's list build): out[j] = in[0] + .. + in[j - 1] for j < m, *total = the sum
+hipError_t launch_scan(const int32_t *in, int32_t *out, int32_t m, int32_t *total, hipStream_t s);
+
 // k_diag_replay: the records of the unplaced pods ul[0, U) at their decision
 // states, out [U][kDiagWords] (zeroed by the caller).  single >= 0: that one
 // unplaced pod instead (U = 1), and with `status` its [n] status bytes rather

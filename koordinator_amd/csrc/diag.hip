@@ -293,6 +293,11 @@ hipError_t launch_diag(const DevCfg &c, const DevNodes &d, const DevPod *pods, i
   return hipGetLastError();
 }
 
+hipError_t launch_scan(const int32_t *in, int32_t *out, int32_t m, int32_t *total, hipStream_t s) {
+  hipLaunchKernelGGL(k_diag_scan, dim3(1), dim3(DIAG_THREADS), 0, s, in, out, m, total);
+  return hipGetLastError();
+}
+
 size_t diag_ws_ints(int32_t n, int32_t P) { return 2 * ((size_t)n + 1) + 4 * (size_t)std::max(P, 0) + 2; }
 
 DiagLists diag_lists(int32_t *ws, int32_t n, int32_t P) {

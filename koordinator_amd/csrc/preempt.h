@@ -1,0 +1,68 @@
+// preempt.h -- launch wrappers of preempt.hip (host side): the preemption dry
+// run, SelectVictimsOnNode on every node and the candidate pick on device.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "eval.hpp"
+
+namespace kh {
+
+// Device copy of one koordhip_assigned (quantities of the pod as exact f64).
+struct DevAsg {
+  DevPod pod;
+  int64_t start;
+  int64_t qreq[KOORDHIP_PREEMPT_QRES];
+  int32_t prio, quota;
+  uint32_t flags, pdb_mask;
+  int32_t idx;  // index into the caller's table
+  int32_t node;
+};
+static_assert(sizeof(DevAsg) == 160 && sizeof(DevAsg) % 16 == 0, "DevAsg is 160 bytes");
+
+// Device copy of one koordhip_preemptor.
+struct DevPre {
+  DevPod pod;
+  int64_t used[KOORDHIP_PREEMPT_QRES], runtime[KOORDHIP_PREEMPT_QRES], req[KOORDHIP_PREEMPT_QRES];
+  int32_t prio, quota;
+  uint32_t qmask, pad;
+};
+static_assert(sizeof(DevPre) == 208, "DevPre is 208 bytes");
+
+struct PdbAllowed {
+  int32_t a[KOORDHIP_PREEMPT_PDBS];
+};
+
+// One workgroup's best candidate of one preemptor (node -1: none): the
+// verdict's own fields are the pick's key.
+struct PreemptPartial {
+  koordhip_preempt_node v;
+  int32_t node, pad;
+};
+static_assert(sizeof(PreemptPartial) == 40, "partials are 40 bytes");
+
+constexpr int PREEMPT_THREADS = 256;
+inline int32_t preempt_blocks(int32_t n) { return (n + PREEMPT_THREADS - 1) / PREEMPT_THREADS; }
+
+// The node-sorted table: node i's pods are sorted[off[i] .. off[i + 1]) in list
+// order (priority descending, start ascending, input index ascending).
+//   raw [m] the records in input order; sorted [m] the permuted copy
+//   ws  int32 workspace of preempt_ws_ints(n, m) words: cnt [n + 1], off [n + 1], nl [m], tot [1]
+size_t preempt_ws_ints(int32_t n, int32_t m);
+inline int32_t *preempt_off(int32_t *ws, int32_t n) { return ws + n + 1; }
+hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s);
+
+// The dry run of pre[0, n_pre) on the current rows.  count [n_pre][5] (zeroed by
+// the caller) receives the nodes per status, part [n_pre][preempt_blocks(n)]
+// the workgroups' best candidates; per_node (n_pre = 1 only, may be NULL) every
+// node's verdict.
+hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                          const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
+                          PreemptPartial *part, koordhip_preempt_node *per_node, hipStream_t s);
+// part -> res[p].node / best (count is copied in), then the chosen nodes'
+// victims [n_pre][max_victims], -1 padded (victims may be NULL).
+hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                               const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
+                               const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
+                               int32_t max_victims, hipStream_t s);
+
+}  // namespace kh

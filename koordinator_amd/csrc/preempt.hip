@@ -1,0 +1,437 @@
+// preempt.hip -- the preemption dry run: elasticquota's SelectVictimsOnNode
+// (preempt.go:111-215) on every node and the pick of one candidate
+// (upstream pickOneNodeForPreemption), against the current rows.  Nothing
+// here writes engine state.
+//
+//   k_pre_count / (k_diag_scan) / k_pre_fill / k_pre_sort / k_pre_permute
+//                     the node-sorted table: per node its assigned pods, each
+//                     list ordered by MoreImportantPod then input index, and a
+//                     permuted COPY of the records so that a thread's list is
+//                     one contiguous run of 160-B records (no index gather in
+//                     the hot kernel).
+//   k_preempt         256-node tiles x preemptor tiles; the tile's preemptors
+//                     are staged in LDS, a thread loads its node row once and
+//                     copies it per preemptor.  The walk over a node's list
+//                     diverges, the loop over preemptors does not: per
+//                     preemptor the wave counts the statuses with ballots and
+//                     reduces the pick's key with shuffles, the workgroup
+//                     writes ONE partial (the best candidate's verdict) per
+//                     preemptor.  No 128-bit key ever meets a global atomic.
+//   k_preempt_pick    one wave per preemptor over the workgroups' partials.
+//   k_preempt_victims one thread per preemptor re-runs its chosen node and
+//                     writes the victims in the reference's append order.
+//
+// Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
+// reads the row the previous add / remove left), so a wave would hold 63 idle
+// lanes per step; with a thread per node the chain's steps of 64 nodes issue
+// together and the records stream through L2 one contiguous run per lane.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "diag.h"
+#include "eval.hpp"
+#include "preempt.h"
+
+namespace kh {
+
+constexpr int PRE_PT = 32;  // preemptors per LDS tile
+constexpr int PRE_WORDS = (int)(sizeof(DevPre) / sizeof(uint64_t));
+constexpr int PRE_WAVES = PREEMPT_THREADS / 64;
+constexpr int ASG_VEC = (int)(sizeof(DevAsg) / sizeof(uint4));
+static_assert(sizeof(DevPre) % sizeof(uint64_t) == 0, "preemptor records are staged as 8-B words");
+static_assert(KOORDHIP_PREEMPT_NODE_PODS == 128, "a node's potential / violating sets are two 64-bit masks");
+
+// ---------------------------------------------------------------------------
+// the node-sorted table
+
+__global__ void k_pre_count(const DevAsg *__restrict__ raw, int32_t m, int32_t n, int32_t *__restrict__ cnt) {
+  const int32_t j = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= m) return;
+  const int32_t node = raw[j].node;
+  if (node >= 0 && node < n) atomicAdd(&cnt[node], 1);
+}
+
+__global__ void k_pre_fill(const DevAsg *__restrict__ raw, int32_t m, int32_t n, const int32_t *__restrict__ off,
+                           int32_t *__restrict__ cur, int32_t *__restrict__ nl) {
+  const int32_t j = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (j >= m) return;
+  const int32_t node = raw[j].node;
+  if (node >= 0 && node < n) nl[off[node] + atomicAdd(&cur[node], 1)] = j;
+}
+
+// MoreImportantPod, then the input index (the engine's rule where Go's unstable sort has none)
+__device__ __forceinline__ bool list_before(int32_t pa, int64_t sa, int32_t ia, int32_t pb, int64_t sb, int32_t ib) {
+  if (pa != pb) return pa > pb;
+  if (sa != sb) return sa < sb;
+  return ia < ib;
+}
+
+// each node's list into list order (the fill's order is arbitrary; lists hold 128 entries at most)
+__global__ void k_pre_sort(const DevAsg *__restrict__ raw, const int32_t *__restrict__ off, int32_t *__restrict__ nl,
+                           int32_t n) {
+  const int32_t i = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const int32_t lo = off[i], hi = off[i + 1];
+  for (int32_t a = lo + 1; a < hi; a++) {
+    const int32_t x = nl[a];
+    const int32_t px = raw[x].prio;
+    const int64_t sx = raw[x].start;
+    int32_t b = a;
+    for (; b > lo; b--) {
+      const int32_t y = nl[b - 1];
+      if (!list_before(px, sx, x, raw[y].prio, raw[y].start, y)) break;
+      nl[b] = y;
+    }
+    nl[b] = x;
+  }
+}
+
+// sorted[j] = raw[nl[j]], 16 bytes per thread
+__global__ void k_pre_permute(const DevAsg *__restrict__ raw, DevAsg *__restrict__ sorted,
+                              const int32_t *__restrict__ nl, int32_t m) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (int64_t)m * ASG_VEC) return;
+  const int32_t j = (int32_t)(g / ASG_VEC), k = (int32_t)(g - (int64_t)j * ASG_VEC);
+  reinterpret_cast<uint4 *>(sorted)[g] = reinterpret_cast<const uint4 *>(raw)[(int64_t)nl[j] * ASG_VEC + k];
+}
+
+// ---------------------------------------------------------------------------
+// one (preemptor, node)
+
+// a is picked before b (na / nb: their nodes, -1 = no candidate)
+__device__ __forceinline__ bool pick_before(const koordhip_preempt_node &a, int32_t na, const koordhip_preempt_node &b,
+                                            int32_t nb) {
+  if (na < 0) return false;
+  if (nb < 0) return true;
+  const bool za = a.n_victims == 0, zb = b.n_victims == 0;
+  if (za != zb) return za;  // a node that needs no victim wins outright
+  if (a.n_pdb_violations != b.n_pdb_violations) return a.n_pdb_violations < b.n_pdb_violations;
+  if (a.top_priority != b.top_priority) return a.top_priority < b.top_priority;
+  if (a.sum_priority != b.sum_priority) return a.sum_priority < b.sum_priority;
+  if (a.n_victims != b.n_victims) return a.n_victims < b.n_victims;
+  if (a.earliest_start != b.earliest_start) return a.earliest_start > b.earliest_start;  // the latest start wins
+  return na < nb;
+}
+
+struct QuotaUsed {
+  int64_t u[KOORDHIP_PREEMPT_QRES];
+};
+
+// RemovePod / AddPod of one listed pod: the row and, for a pod the quota
+// counts, the quota's used (SubtractWithNonNegativeResult / Add, plugin.go:296-305)
+__device__ __forceinline__ void move_pod(NV &w, QuotaUsed &q, const DevAsg &a, int sign) {
+  apply_delta(w, a.pod, sign);
+  if (a.flags & KOORDHIP_ASG_IN_QUOTA) {
+#pragma unroll
+    for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++)
+      q.u[r] = sign > 0 ? q.u[r] + a.qreq[r] : (q.u[r] > a.qreq[r] ? q.u[r] - a.qreq[r] : 0);
+  }
+}
+
+// SelectVictimsOnNode of preemptor P on the node whose row is v and whose
+// listed pods are list[0, len).  EMIT: the victims' table indices go to
+// vout[0, vmax) in append order.
+template <bool EMIT>
+__device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
+                                                              const NumaRowRS<1> &nr, const DevAsg *__restrict__ list,
+                                                              int32_t len, const PdbAllowed &pdb, const DevPre &P,
+                                                              int32_t *vout, int32_t vmax) {
+  koordhip_preempt_node r{};
+  const DevPod pod = P.pod;
+  if (filter_status(c, pod, v, nr, classes, 0, 0u) & KOORDHIP_ST_STATIC_FAIL) {
+    r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
+    return r;
+  }
+  const int32_t pprio = P.prio, pquota = P.quota;
+  NV w = v;
+  QuotaUsed q;
+  int32_t pa[KOORDHIP_PREEMPT_PDBS];
+#pragma unroll
+  for (int k = 0; k < KOORDHIP_PREEMPT_QRES; k++) q.u[k] = P.used[k];
+#pragma unroll
+  for (int b = 0; b < KOORDHIP_PREEMPT_PDBS; b++) pa[b] = pdb.a[b];
+  // remove every pod canPreempt accepts; the PDB split walks the same pods in the same order
+  uint64_t pot0 = 0, pot1 = 0, vio0 = 0, vio1 = 0;
+  for (int32_t k = 0; k < len; k++) {
+    const DevAsg &a = list[k];
+    if ((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota) continue;
+    move_pod(w, q, a, -1);
+    const uint32_t pm = a.pdb_mask;
+    bool bad = false;
+#pragma unroll
+    for (int b = 0; b < KOORDHIP_PREEMPT_PDBS; b++)
+      if ((pm >> b) & 1u) {
+        pa[b]--;
+        bad = bad || pa[b] < 0;
+      }
+    const uint64_t bit = 1ull << (k & 63);
+    if (k < 64) {
+      pot0 |= bit;
+      if (bad) vio0 |= bit;
+    } else {
+      pot1 |= bit;
+      if (bad) vio1 |= bit;
+    }
+  }
+  if (!(pot0 | pot1)) {
+    r.status = KOORDHIP_PREEMPT_NO_VICTIMS;
+    return r;
+  }
+  if (filter_status(c, pod, w, nr, classes, 0, 0u) != 0u) {
+    r.status = KOORDHIP_PREEMPT_UNFIT;
+    return r;
+  }
+  // reprieve: the violating group first, then the rest, each in list order
+  int32_t nv = 0, npdb = 0, top = 0, maxp = 0;
+  int64_t sum = 0, es = 0;
+  for (int g = 0; g < 4; g++) {
+    const bool violating = g < 2;
+    uint64_t m = (g & 1) ? pot1 : pot0;
+    const uint64_t vm = (g & 1) ? vio1 : vio0;
+    m &= violating ? vm : ~vm;
+    while (m) {
+      const int32_t k = (int32_t)__ffsll((unsigned long long)m) - 1 + ((g & 1) ? 64 : 0);
+      m &= m - 1;
+      const DevAsg &a = list[k];
+      move_pod(w, q, a, +1);
+      const bool fits = filter_status(c, pod, w, nr, classes, 0, 0u) == 0u;
+      if (!fits) move_pod(w, q, a, -1);
+      bool over = false;
+      if (pquota >= 0) {
+#pragma unroll
+        for (int d = 0; d < KOORDHIP_PREEMPT_QRES; d++)
+          if ((P.qmask >> d) & 1u) over = over || q.u[d] + P.req[d] > P.runtime[d];
+      }
+      if (!fits && over) {  // the second RemovePod of one pod fails: the evaluator drops the node
+        koordhip_preempt_node e{};
+        e.status = KOORDHIP_PREEMPT_ERROR;
+        return e;
+      }
+      if (fits && !over) continue;  // reprieved
+      if (over) move_pod(w, q, a, -1);
+      if (!fits && violating) npdb++;
+      const int32_t ap = a.prio;
+      const int64_t as = a.start;
+      if (nv == 0) top = ap;
+      if (nv == 0 || ap > maxp) {
+        maxp = ap;
+        es = as;
+      } else if (ap == maxp && as < es) {
+        es = as;
+      }
+      sum += (int64_t)ap + (1ll << 31);
+      if constexpr (EMIT) {
+        if (nv < vmax) vout[nv] = a.idx;
+      }
+      nv++;
+    }
+  }
+  r.status = KOORDHIP_PREEMPT_CANDIDATE;
+  r.n_victims = nv;
+  r.n_pdb_violations = npdb;
+  r.top_priority = top;
+  r.sum_priority = sum;
+  r.earliest_start = es;
+  return r;
+}
+
+// The dry run's envelope as the compiler sees it: only NodeResourcesFit,
+// LoadAware and the static filters can be in the Filter (launch_preempt refuses
+// the rest) and no Score is read, so with these masks the NodeNUMAResource and
+// Reservation halves of filter_status and their row fields fold away.
+__device__ __forceinline__ DevCfg envelope(DevCfg c) {
+  c.filt &= KOORDHIP_PLUGIN_FIT | KOORDHIP_PLUGIN_LOADAWARE | KOORDHIP_PLUGIN_NODE_STATIC;
+  c.score = 0;
+  c.resv = 0;
+  c.zones = 0;
+  c.amp = 0;
+  return c;
+}
+
+// ---------------------------------------------------------------------------
+// k_preempt
+
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                             const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                             const DevPre *__restrict__ pre, int32_t n_pre,
+                                                             int32_t *__restrict__ count,
+                                                             PreemptPartial *__restrict__ part,
+                                                             koordhip_preempt_node *__restrict__ per_node) {
+  const DevCfg c = envelope(cfg);
+  __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
+  __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
+  __shared__ PreemptPartial sbest[PRE_PT][PRE_WAVES];
+  const int t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
+  const int32_t p0 = (int32_t)blockIdx.y * PRE_PT;
+  const int32_t np = min(PRE_PT, n_pre - p0);
+  const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
+  for (int32_t w = t; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
+  for (int32_t w = t; w < np * KOORDHIP_PREEMPT_STATUSES; w += PREEMPT_THREADS) scnt[w] = 0;
+  __syncthreads();
+  const DevPre *sp = reinterpret_cast<const DevPre *>(spw);
+  const int32_t i = (int32_t)blockIdx.x * PREEMPT_THREADS + t;
+  const bool live = i < d.n;
+  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
+  NV v{};
+  const Need all = need_all(c);
+  load_node(v, d, il, all, c);
+  NumaRowRS<1> nr{};
+  load_numa<true>(nr, d, il, all);
+  const int32_t lo = off[il];
+  const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+  const DevAsg *list = tab + lo;
+  for (int32_t q = 0; q < np; q++) {
+    koordhip_preempt_node r{};
+    if (live) r = preempt_node<false>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0);
+    const int32_t st = live ? r.status : -1;
+#pragma unroll
+    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
+      const uint64_t mk = __ballot(st == s);
+      if (lane == 0 && mk) atomicAdd(&scnt[q * KOORDHIP_PREEMPT_STATUSES + s], (int32_t)__popcll(mk));
+    }
+    if (per_node && live) per_node[(size_t)q * d.n + i] = r;
+    int32_t bn = st == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      koordhip_preempt_node x;
+      x.status = KOORDHIP_PREEMPT_CANDIDATE;
+      x.n_victims = __shfl_xor(r.n_victims, o, 64);
+      x.n_pdb_violations = __shfl_xor(r.n_pdb_violations, o, 64);
+      x.top_priority = __shfl_xor(r.top_priority, o, 64);
+      x.sum_priority = __shfl_xor((long long)r.sum_priority, o, 64);
+      x.earliest_start = __shfl_xor((long long)r.earliest_start, o, 64);
+      const int32_t xn = __shfl_xor(bn, o, 64);
+      if (pick_before(x, xn, r, bn)) {
+        r = x;
+        bn = xn;
+      }
+    }
+    if (lane == 0) {
+      PreemptPartial b{};
+      if (bn >= 0) b.v = r;
+      b.node = bn;
+      sbest[q][wave] = b;
+    }
+  }
+  __syncthreads();
+  if (t < np) {
+    PreemptPartial b = sbest[t][0];
+#pragma unroll
+    for (int w = 1; w < PRE_WAVES; w++) {
+      const PreemptPartial x = sbest[t][w];
+      if (pick_before(x.v, x.node, b.v, b.node)) b = x;
+    }
+    part[(size_t)(p0 + t) * gridDim.x + blockIdx.x] = b;
+  }
+  for (int32_t w = t; w < np * KOORDHIP_PREEMPT_STATUSES; w += PREEMPT_THREADS) {
+    const int32_t x = scnt[w];
+    if (x) atomicAdd(&count[(size_t)p0 * KOORDHIP_PREEMPT_STATUSES + w], x);
+  }
+}
+
+// one wave per preemptor over its nb partials
+__global__ __launch_bounds__(64) void k_preempt_pick(const PreemptPartial *__restrict__ part, int32_t nb,
+                                                     const int32_t *__restrict__ count,
+                                                     koordhip_preempt_result *__restrict__ res) {
+  const int32_t p = (int32_t)blockIdx.x;
+  const int lane = threadIdx.x;
+  PreemptPartial b{};
+  b.node = -1;
+  for (int32_t k = lane; k < nb; k += 64) {
+    const PreemptPartial x = part[(size_t)p * nb + k];
+    if (pick_before(x.v, x.node, b.v, b.node)) b = x;
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    PreemptPartial x{};
+    x.v.n_victims = __shfl_xor(b.v.n_victims, o, 64);
+    x.v.n_pdb_violations = __shfl_xor(b.v.n_pdb_violations, o, 64);
+    x.v.top_priority = __shfl_xor(b.v.top_priority, o, 64);
+    x.v.sum_priority = __shfl_xor((long long)b.v.sum_priority, o, 64);
+    x.v.earliest_start = __shfl_xor((long long)b.v.earliest_start, o, 64);
+    x.node = __shfl_xor(b.node, o, 64);
+    if (pick_before(x.v, x.node, b.v, b.node)) b = x;
+  }
+  if (lane == 0) {
+    koordhip_preempt_result r{};
+    r.node = b.node;
+    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) r.count[s] = count[(size_t)p * KOORDHIP_PREEMPT_STATUSES + s];
+    if (b.node >= 0) {
+      r.best = b.v;
+      r.best.status = KOORDHIP_PREEMPT_CANDIDATE;
+    }
+    res[p] = r;
+  }
+}
+
+// one thread per preemptor: its chosen node again, writing the victims (vout is -1 filled by the caller)
+__global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                        const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                        const DevPre *__restrict__ pre, int32_t n_pre,
+                                                        const koordhip_preempt_result *__restrict__ res,
+                                                        int32_t *__restrict__ vout, int32_t vmax) {
+  const DevCfg c = envelope(cfg);
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n_pre) return;
+  const int32_t i = res[p].node;
+  if (i < 0 || i >= d.n) return;
+  NV v{};
+  const Need all = need_all(c);
+  load_node(v, d, i, all, c);
+  NumaRowRS<1> nr{};
+  load_numa<true>(nr, d, i, all);
+  const int32_t lo = off[i];
+  const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
+  const DevPre P = pre[p];
+  (void)preempt_node<true>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax);
+}
+
+// ---------------------------------------------------------------------------
+// host-side launch wrappers
+
+size_t preempt_ws_ints(int32_t n, int32_t m) { return 2 * ((size_t)n + 1) + (size_t)std::max(m, 0) + 1; }
+
+hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s) {
+  int32_t *cnt = ws, *off = preempt_off(ws, n), *nl = off + n + 1, *tot = nl + std::max(m, 0);
+  hipError_t e = hipMemsetAsync(cnt, 0, ((size_t)n + 1) * sizeof(int32_t), s);
+  if (e != hipSuccess) return e;
+  if (m <= 0) return hipMemsetAsync(off, 0, ((size_t)n + 1) * sizeof(int32_t), s);
+  const dim3 mg((m + 255) / 256), blk(256);
+  hipLaunchKernelGGL(k_pre_count, mg, blk, 0, s, raw, m, n, cnt);
+  e = launch_scan(cnt, off, n + 1, tot, s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(cnt, 0, ((size_t)n + 1) * sizeof(int32_t), s);  // now the fill's cursors
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_pre_fill, mg, blk, 0, s, raw, m, n, off, cnt, nl);
+  if (n > 0) hipLaunchKernelGGL(k_pre_sort, dim3((n + 255) / 256), blk, 0, s, raw, off, nl, n);
+  const int64_t words = (int64_t)m * ASG_VEC;
+  hipLaunchKernelGGL(k_pre_permute, dim3((unsigned)((words + 255) / 256)), blk, 0, s, raw, sorted, nl, m);
+  return hipGetLastError();
+}
+
+hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                          const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
+                          PreemptPartial *part, koordhip_preempt_node *per_node, hipStream_t s) {
+  if (n_pre <= 0 || d.n <= 0) return hipSuccess;
+  if (c.resv || (c.filt & (KOORDHIP_PLUGIN_NUMA | KOORDHIP_PLUGIN_RESERVATION))) return hipErrorInvalidValue;
+  if (per_node && n_pre != 1) return hipErrorInvalidValue;
+  const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_preempt, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node);
+  return hipGetLastError();
+}
+
+hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                               const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
+                               const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
+                               int32_t max_victims, hipStream_t s) {
+  if (n_pre <= 0 || d.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
+  if (victims && max_victims > 0)
+    hipLaunchKernelGGL(k_preempt_victims, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res,
+                       victims, max_victims);
+  return hipGetLastError();
+}
+
+}  // namespace kh

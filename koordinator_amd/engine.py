@@ -271,6 +271,36 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_fetch_node_status(self._ctx, int(pod_index), abi.ptr(out, C.c_uint8)))
         return out
 
+    # ---- preemption dry run (koordinator_amd.preemption builds the records)
+    def preempt_load_pods(self, assigned: np.ndarray, pdb_allowed=()):
+        """Upload the table of the pods that sit on the nodes (abi.ASSIGNED_DTYPE)
+        and the PDBs' DisruptionsAllowed; valid until the next call or load_snapshot."""
+        a = np.ascontiguousarray(assigned, dtype=abi.ASSIGNED_DTYPE)
+        pdb = np.ascontiguousarray(pdb_allowed, dtype=np.int32)
+        abi.check(self.lib, self.lib.koordhip_preempt_load_pods(self._ctx, a.ctypes.data, len(a),
+                                                                abi.ptr(pdb, C.c_int32), len(pdb)))
+
+    def preempt(self, preemptors: np.ndarray, max_victims: int = 0):
+        """SelectVictimsOnNode on every node and the candidate pick, per
+        preemptor (abi.PREEMPTOR_DTYPE) against the current state: returns
+        (abi.PREEMPT_RESULT_DTYPE [p], victims [p][max_victims] as indices into
+        the loaded table, -1 padded).  Writes no engine state."""
+        pre = np.ascontiguousarray(np.atleast_1d(preemptors), dtype=abi.PREEMPTOR_DTYPE)
+        out = np.zeros(len(pre), abi.PREEMPT_RESULT_DTYPE)
+        vic = np.full((len(pre), max_victims), -1, np.int32)
+        abi.check(self.lib, self.lib.koordhip_preempt(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
+                                                      abi.ptr(vic, C.c_int32) if max_victims else None, max_victims))
+        return out, vic
+
+    def preempt_node_verdicts(self, preemptor) -> np.ndarray:
+        """One preemptor's verdict on every node (abi.PREEMPT_NODE_DTYPE [n])."""
+        pre = np.ascontiguousarray(np.atleast_1d(preemptor), dtype=abi.PREEMPTOR_DTYPE)
+        if len(pre) != 1:
+            raise ValueError("preempt_node_verdicts takes one preemptor")
+        out = np.zeros(self.n, abi.PREEMPT_NODE_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_preempt_node_verdicts(self._ctx, pre.ctypes.data, out.ctypes.data))
+        return out
+
     def last_stats(self) -> dict:
         em, tm = C.c_double(), C.c_double()
         nl, ne = C.c_int64(), C.c_int64()

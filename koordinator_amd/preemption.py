@@ -1,0 +1,163 @@
+"""Host side of the preemption dry run (koordhip_preempt*): the table of the
+pods that sit on the nodes, the preemptor records and a view of the result.
+
+    assigned_records   k8s pods on nodes -> abi.ASSIGNED_DTYPE (priority, start
+                       time, non-preemptible label, quota name -> id, pdb_mask
+                       from the PDB objects as preempt.go:222-267 matches them)
+    preemptor_records  pending pods + their quotas' postFilterState -> abi.PREEMPTOR_DTYPE
+    PreemptionResult   node name + victim pod keys of one preemptor
+
+PodEligibleToPreemptOthers and nominated pods stay with the caller.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass, field
+from typing import Callable, Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+
+from . import abi, k8s
+from .config import Profile
+from .marshal import MarshalError, pod_record
+from .topologyspread import LabelSelector
+
+LABEL_QUOTA_NAME = "quota.scheduling.koordinator.sh/name"           # apis/extension/elastic_quota.go:37
+LABEL_PREEMPTIBLE = "quota.scheduling.koordinator.sh/preemptible"   # :42
+DEFAULT_QUOTA_NAME = "koordinator-default-quota"
+QUOTA_RESOURCES = (k8s.CPU, k8s.MEMORY)                             # the default quota dimensions (<= PREEMPT_QRES)
+
+
+@dataclass
+class PodDisruptionBudget:
+    """policy/v1 PodDisruptionBudget as filterPodsWithPDBViolation reads it."""
+    namespace: str = "default"
+    name: str = "pdb"
+    selector: Optional[LabelSelector] = None     # None: LabelSelectorAsSelector(nil) matches nothing
+    disruptions_allowed: int = 0                 # Status.DisruptionsAllowed
+    disrupted_pods: Sequence[str] = ()           # Status.DisruptedPods keys (pod names)
+
+
+@dataclass
+class QuotaState:
+    """postFilterState of a pending pod's quota (plugin.go PreFilter): used and
+    runtime as resource lists; `skip` when the plugin's PreFilter skipped."""
+    used: k8s.ResourceList = field(default_factory=dict)
+    runtime: k8s.ResourceList = field(default_factory=dict)
+    skip: bool = False
+
+
+def is_non_preemptible(pod: k8s.Pod) -> bool:
+    """extension.IsPodNonPreemptible (elastic_quota.go:79-81)."""
+    return (pod.labels or {}).get(LABEL_PREEMPTIBLE) == "false"
+
+
+def quota_name(pod: k8s.Pod) -> str:
+    """The pod's quota label, else the default quota (the namespace fallback of
+    getPodAssociateQuotaName needs the ElasticQuota lister: pass your own `quota_of`)."""
+    return (pod.labels or {}).get(LABEL_QUOTA_NAME) or DEFAULT_QUOTA_NAME
+
+
+def pdb_matches(pdb: PodDisruptionBudget, pod: k8s.Pod) -> bool:
+    """preempt.go:231-250: same namespace, a non-empty selector that matches, the
+    pod not among the PDB's DisruptedPods; a pod without labels matches no PDB."""
+    if not pod.labels or pdb.namespace != pod.namespace or pdb.selector is None:
+        return False
+    sel = pdb.selector
+    if not sel.match_labels and not sel.match_expressions:
+        return False
+    return sel.matches(pod.labels) and pod.name not in pdb.disrupted_pods
+
+
+def _quantities(rlist: k8s.ResourceList, resources) -> List[int]:
+    out = [0] * abi.PREEMPT_QRES
+    for d, name in enumerate(resources):
+        if name in rlist:
+            out[d] = k8s.resource_value(name, rlist[name])
+    return out
+
+
+class QuotaIds:
+    """quota name -> the id the records carry (host-assigned, dense from 0)."""
+
+    def __init__(self):
+        self.ids: Dict[str, int] = {}
+
+    def of(self, name: str) -> int:
+        return self.ids.setdefault(name, len(self.ids))
+
+
+def assigned_records(pods: Iterable[k8s.Pod], profile: Profile, node_index: Dict[str, int], quotas: QuotaIds,
+                     pdbs: Sequence[PodDisruptionBudget] = (), now_ns: int = 0,
+                     start_time_ns: Optional[Dict[str, int]] = None, in_quota: Optional[Callable[[k8s.Pod], bool]] = None,
+                     quota_of: Callable[[k8s.Pod], str] = quota_name, resources=QUOTA_RESOURCES, static_classes=None):
+    """(abi.ASSIGNED_DTYPE records, DisruptionsAllowed per PDB, pod keys) of the
+    pods bound to the snapshot's nodes (pod.node_name in `node_index`).
+    `start_time_ns`: status.startTime by pod key (absent: `now_ns`, as
+    GetPodStartTime).  `in_quota(pod)`: quotaInfo.IsPodExist (default: every pod)."""
+    if len(pdbs) > abi.PREEMPT_PDBS:
+        raise MarshalError(f"{len(pdbs)} PodDisruptionBudgets: the table takes {abi.PREEMPT_PDBS}")
+    if len(resources) > abi.PREEMPT_QRES:
+        raise MarshalError(f"{len(resources)} quota dimensions: the records take {abi.PREEMPT_QRES}")
+    pods = [p for p in pods if p.node_name in node_index]
+    out = np.zeros(len(pods), abi.ASSIGNED_DTYPE)
+    for j, pod in enumerate(pods):
+        rec = out[j]
+        pod_record(pod, profile, rec["pod"], static_classes=static_classes)
+        rec["node"] = node_index[pod.node_name]
+        rec["priority"] = pod.priority or 0
+        rec["start_time"] = (start_time_ns or {}).get(pod.key, now_ns)
+        rec["quota"] = quotas.of(quota_of(pod))
+        rec["flags"] = ((abi.ASG_NONPREEMPTIBLE if is_non_preemptible(pod) else 0) |
+                        (abi.ASG_IN_QUOTA if in_quota is None or in_quota(pod) else 0))
+        rec["pdb_mask"] = sum(1 << i for i, pdb in enumerate(pdbs) if pdb_matches(pdb, pod))
+        reqs, _ = k8s.pod_requests_and_limits(pod)
+        rec["qreq"] = _quantities(reqs, resources)
+    return out, np.array([p.disruptions_allowed for p in pdbs], np.int32), [p.key for p in pods]
+
+
+def preemptor_records(pods: Iterable[k8s.Pod], profile: Profile, quotas: QuotaIds, states: Dict[str, QuotaState],
+                      quota_of: Callable[[k8s.Pod], str] = quota_name, resources=QUOTA_RESOURCES,
+                      static_classes=None) -> np.ndarray:
+    """abi.PREEMPTOR_DTYPE records; states: quota name -> its postFilterState
+    (absent or skip: quota -1, no quota check and no victims)."""
+    pods = list(pods)
+    out = np.zeros(len(pods), abi.PREEMPTOR_DTYPE)
+    for j, pod in enumerate(pods):
+        rec = out[j]
+        pod_record(pod, profile, rec["pod"], static_classes=static_classes)
+        rec["priority"] = pod.priority or 0
+        name = quota_of(pod)
+        st = states.get(name)
+        if st is None or st.skip:
+            rec["quota"] = -1
+            continue
+        rec["quota"] = quotas.of(name)
+        rec["q_used"] = _quantities(st.used, resources)
+        rec["q_runtime"] = _quantities(st.runtime, resources)
+        reqs, _ = k8s.pod_requests_and_limits(pod)
+        rec["q_req"] = _quantities(reqs, resources)
+        rec["q_mask"] = sum(1 << d for d, r in enumerate(resources) if r in st.runtime)
+    return out
+
+
+@dataclass
+class PreemptionResult:
+    """One preemptor's koordhip_preempt_result with names: the nominated node
+    (None: no candidate), the victims' pod keys in the reference's order, the
+    nodes per status."""
+    node: Optional[str]
+    victims: List[str]
+    n_victims: int
+    n_pdb_violations: int
+    counts: Dict[str, int]
+
+    STATUS_NAMES = ("candidate", "no_victims", "unfit", "error", "unresolvable")
+
+    @classmethod
+    def of(cls, result, victims, node_names: Sequence[str], pod_keys: Sequence[str]) -> "PreemptionResult":
+        node = int(result["node"])
+        return cls(node=node_names[node] if node >= 0 else None,
+                   victims=[pod_keys[int(v)] for v in victims if v >= 0],
+                   n_victims=int(result["best"]["n_victims"]),
+                   n_pdb_violations=int(result["best"]["n_pdb_violations"]),
+                   counts={s: int(result["count"][k]) for k, s in enumerate(cls.STATUS_NAMES)})
