@@ -781,6 +781,34 @@ int koordhip_preempt(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n
 int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *pre,
                                    koordhip_preempt_node *per_node /* [n] */);
 
+/* ---- sequential preemption dry run (additive to ABI 15: detect it by the symbol)
+ * The same dry run for a batch whose answers have to hold together: the
+ * preemptors are processed in input order and preemptor k gets the verdicts
+ * and the pick of koordhip_preempt on the state S_k the earlier ones left.
+ * For every earlier preemptor j that ended with a node c >= 0 and the (full)
+ * victim list V_j:
+ *   - the pods of V_j are gone: off their nodes' rows, never a potential
+ *     victim, no PDB budget consumed in the split;
+ *   - j's own pod is on the row of c iff priority_j >= priority_k (upstream's
+ *     RunFilterPluginsWithNominatedPods); a nominated pod is never a victim;
+ *   - per victim and per bit b of its pdb_mask: allowed[b] = max(0, allowed[b] - 1);
+ *   - if quota_k == quota_j >= 0, q_used_k = max(0, q_used_k - sum of qreq of
+ *     V_j's KOORDHIP_ASG_IN_QUOTA pods) per dimension.  Every q_used is given
+ *     AS OF THE START OF THE CALL; the nominated pod is not added to it.
+ * out[k] / victims[k] are those of koordhip_preempt on S_k.  A preemptor that
+ * ends with node = -1 changes nothing.  The call writes no engine state and
+ * leaves the loaded table as it was; envelope and error codes are those of
+ * koordhip_preempt.  One host synchronisation, at the end. */
+typedef struct koordhip_preempt_stream_stats {
+  int64_t full_recomputes;  /* preemptors for which a changed PDB budget / freed quota made every 256-node block evaluate again */
+  int64_t block_recomputes; /* blocks evaluated again, over all preemptors */
+  int64_t blocks_skipped;   /* blocks whose evaluation on the loaded state was kept */
+} koordhip_preempt_stream_stats;
+int koordhip_preempt_stream(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n_pre,
+                            koordhip_preempt_result *out /* [n_pre] */,
+                            int32_t *victims /* [n_pre][max_victims], may be NULL */, int32_t max_victims,
+                            koordhip_preempt_stream_stats *stats /* may be NULL */);
+
 /* The same split in two so a caller can time the device part alone: stage
  * (host -> HBM copy) then place (HBM-resident pods, result kept on device
  * until koordhip_fetch_placements). */

@@ -255,6 +255,10 @@ PREEMPT_RESULT_DTYPE = np.dtype([("node", "<i4"), ("count", "<i4", (PREEMPT_STAT
                                 align=True)
 assert (ASSIGNED_DTYPE.itemsize, PREEMPTOR_DTYPE.itemsize, PREEMPT_NODE_DTYPE.itemsize,
         PREEMPT_RESULT_DTYPE.itemsize) == (160, 208, 32, 56)
+# koordhip_preempt_stream_stats (24 bytes) of the sequential dry run
+PREEMPT_STREAM_STATS_DTYPE = np.dtype([("full_recomputes", "<i8"), ("block_recomputes", "<i8"), ("blocks_skipped", "<i8")],
+                                      align=True)
+assert PREEMPT_STREAM_STATS_DTYPE.itemsize == 24
 # numpy twin of koordhip_pod_ext (176 bytes)
 POD_EXT_DTYPE = np.dtype([
     ("dev_req", "<i8", (DEV_TYPES, DEV_RES)),
@@ -347,6 +351,7 @@ def load_library(path: str = LIB_PATH):
         "koordhip_preempt_load_pods": (C.c_int, [vp, vp, C.c_int32, _i32p, C.c_int32]),
         "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
+        "koordhip_preempt_stream": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32, vp]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -381,6 +386,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_commit_ext", "koordhip_uncommit_ext",
     "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
+    "koordhip_preempt_stream",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

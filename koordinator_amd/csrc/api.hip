@@ -273,7 +273,8 @@ struct koordhip_ctx {
   void *d_pre_ws = nullptr;        // the lists' workspace (kh::preempt_ws_ints; off lives here)
   void *d_pre_in = nullptr;        // the preemptors
   void *d_pre_out = nullptr;       // counts, partials, results, victims / the per-node verdicts
-  size_t pre_raw_cap = 0, pre_tab_cap = 0, pre_ws_cap = 0, pre_in_cap = 0, pre_out_cap = 0;
+  void *d_pre_st = nullptr;        // koordhip_preempt_stream's call-scoped state (kh::StreamState)
+  size_t pre_raw_cap = 0, pre_tab_cap = 0, pre_ws_cap = 0, pre_in_cap = 0, pre_out_cap = 0, pre_st_cap = 0;
 };
 
 namespace {
@@ -1294,7 +1295,8 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_podx, (void *)c->d_devout, (void *)c->d_seqg, c->d_seqdesc, (void *)c->d_pod_cls,
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
                   (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
-                  c->d_diag_rec, c->d_diag_pods, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out})
+                  c->d_diag_rec, c->d_diag_pods, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out,
+                  c->d_pre_st})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
     if (c->ev_res[i]) (void)hipEventDestroy(c->ev_res[i]);
@@ -3899,6 +3901,83 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
                                   c->stream));
   HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, d_vic, vb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The sequential dry run: every buffer that changes during the call is carved
+// out of d_pre_st and initialised here; the rows, the table and pre_pdb are read only.
+int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                            int32_t *victims, int32_t max_victims, koordhip_preempt_stream_stats *stats) {
+  static_assert(sizeof(koordhip_preempt_stream_stats) == 24, "stream stats");
+  if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
+  if (int e = preempt_ready(c, pre, n_pre)) return e;
+  if (stats) *stats = koordhip_preempt_stream_stats{};
+  if (n_pre == 0) return 0;
+  const int32_t n = c->n;
+  const size_t nv = victims ? (size_t)n_pre * max_victims : 0;
+  if (n == 0) {
+    std::memset(out, 0, (size_t)n_pre * sizeof(*out));
+    for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
+    for (size_t k = 0; k < nv; k++) victims[k] = -1;
+    return 0;
+  }
+  const size_t nb = (size_t)kh::preempt_blocks(n);
+  size_t at = 0;
+  auto take = [&at](size_t bytes) {
+    const size_t o = at;
+    at += (bytes + 15) & ~(size_t)15;
+    return o;
+  };
+  // cleared to 0 before the first launch: gone .. stats
+  const size_t o_gone = take((size_t)n * 2 * sizeof(uint64_t));
+  const size_t o_freed = take((size_t)n_pre * KOORDHIP_PREEMPT_QRES * sizeof(int64_t));
+  const size_t o_touched = take(nb * sizeof(int32_t));
+  const size_t o_qflag = take((size_t)n_pre * sizeof(int32_t));
+  const size_t o_stats = take(sizeof(koordhip_preempt_stream_stats));
+  const size_t zero_bytes = at;
+  // set to -1: head, victims
+  const size_t o_head = take((size_t)n * sizeof(int32_t));
+  const size_t o_vic = take(nv * sizeof(int32_t));
+  const size_t ff_bytes = at - o_head;
+  // written before they are read
+  const size_t o_part = take((size_t)n_pre * nb * sizeof(kh::PreemptPartial));
+  const size_t o_bcnt = take((size_t)n_pre * nb * KOORDHIP_PREEMPT_STATUSES * sizeof(int32_t));
+  const size_t o_res = take((size_t)n_pre * sizeof(koordhip_preempt_result));
+  const size_t o_nom = take((size_t)n_pre * sizeof(kh::NomEntry));
+  const size_t o_pdb = take(sizeof(kh::PdbAllowed));
+  const size_t o_flags = take(sizeof(kh::StreamFlags));
+  const size_t o_vpos = take(KOORDHIP_PREEMPT_NODE_PODS * sizeof(int32_t));
+  if (int e = ensure(c, &c->d_pre_st, &c->pre_st_cap, at)) return e;
+  char *base = static_cast<char *>(c->d_pre_st);
+  kh::StreamState st{};
+  st.gone = reinterpret_cast<uint64_t *>(base + o_gone);
+  st.freed = reinterpret_cast<int64_t *>(base + o_freed);
+  st.touched = reinterpret_cast<int32_t *>(base + o_touched);
+  st.qflag = reinterpret_cast<int32_t *>(base + o_qflag);
+  st.stats = reinterpret_cast<koordhip_preempt_stream_stats *>(base + o_stats);
+  st.head = reinterpret_cast<int32_t *>(base + o_head);
+  st.victims = nv ? reinterpret_cast<int32_t *>(base + o_vic) : nullptr;
+  st.part = reinterpret_cast<kh::PreemptPartial *>(base + o_part);
+  st.bcnt = reinterpret_cast<int32_t *>(base + o_bcnt);
+  st.res = reinterpret_cast<koordhip_preempt_result *>(base + o_res);
+  st.nom = reinterpret_cast<kh::NomEntry *>(base + o_nom);
+  st.pdb = reinterpret_cast<kh::PdbAllowed *>(base + o_pdb);
+  st.flags = reinterpret_cast<kh::StreamFlags *>(base + o_flags);
+  st.vpos = reinterpret_cast<int32_t *>(base + o_vpos);
+  // A/B knob, read at every call: every block evaluates every preemptor again (the plain per-preemptor chain)
+  const char *fe = std::getenv("KOORDHIP_PREEMPT_STREAM_FULL");
+  const bool full = fe && *fe && std::strcmp(fe, "0") != 0;
+  HIP_TRY(hipMemsetAsync(base, 0, zero_bytes, c->stream));
+  HIP_TRY(hipMemsetAsync(base + o_head, 0xFF, ff_bytes, c->stream));
+  HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
+                                    kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
+                                    static_cast<const kh::DevPre *>(c->d_pre_in), n_pre, st, max_victims, full,
+                                    c->stream));
+  HIP_TRY(hipMemcpyAsync(out, st.res, (size_t)n_pre * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  if (nv) HIP_TRY(hipMemcpyAsync(victims, st.victims, nv * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, sizeof(*stats), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -65,4 +65,49 @@ hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg 
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
                                int32_t max_victims, hipStream_t s);
 
+// ---- the sequential dry run (koordhip_preempt_stream) ----------------------
+// Preemptor k is answered on the state the preemptors before it left: their
+// victims gone, they themselves nominated on their nodes, the PDB budgets and
+// their quotas' used lowered.  All of it lives in the call's own buffers.
+
+// One nominated preemptor on its node's overlay list (entry k is preemptor k's).
+struct NomEntry {
+  DevPod pod;
+  int32_t prio, next;  // next entry of the same node, -1: none
+};
+static_assert(sizeof(NomEntry) == 104, "NomEntry is 104 bytes");
+
+struct StreamFlags {
+  int32_t pdb;   // the budgets differ from the loaded ones
+  int32_t full;  // KOORDHIP_PREEMPT_STREAM_FULL: every block evaluates every preemptor again
+};
+
+// The call's device state.  The caller clears gone, freed, touched, qflag and
+// stats and sets head and victims to -1 before launch_preempt_stream, which
+// writes pdb and flags itself; the rest is written before it is read.
+struct StreamState {
+  PreemptPartial *part;   // [n_pre][nb]    a block's best candidate
+  int32_t *bcnt;          // [n_pre][nb][5] a block's nodes per status
+  koordhip_preempt_result *res;  // [n_pre]
+  uint64_t *gone;         // [n][2] bit k: position k of the node's list is gone
+  NomEntry *nom;          // [n_pre]
+  int32_t *head;          // [n] first overlay entry of the node, -1: none
+  PdbAllowed *pdb;        // the current budgets
+  int64_t *freed;         // [n_pre][QRES] what earlier preemptors of the same quota freed
+  int32_t *touched;       // [nb] the block's rows / lists differ from the loaded state
+  int32_t *qflag;         // [n_pre] freed[k] is not zero
+  StreamFlags *flags;
+  koordhip_preempt_stream_stats *stats;
+  int32_t *vpos;          // [KOORDHIP_PREEMPT_NODE_PODS] the chosen node's victims as list positions
+  int32_t *victims;       // [n_pre][max_victims], -1 filled (may be NULL)
+};
+
+// Phase 1 (the preemptors on the loaded state, per-block partials and counts,
+// a tile of 32 at a time) and per preemptor k: k_preempt_seq (the blocks that
+// have to evaluate k again), k_preempt_seq_pick, k_preempt_apply.  full: the
+// A/B knob, every block evaluates every preemptor again.  Nothing synchronises.
+hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                                 const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
+                                 int32_t max_victims, bool full, hipStream_t s);
+
 }  // namespace kh

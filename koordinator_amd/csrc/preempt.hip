@@ -20,6 +20,15 @@
 //   k_preempt_pick    one wave per preemptor over the workgroups' partials.
 //   k_preempt_victims one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
+//   k_preempt_blk / k_preempt_seq / k_preempt_seq_pick / k_preempt_apply
+//                     the sequential dry run (koordhip_preempt_stream): the
+//                     preemptors in input order, each on the state the earlier
+//                     ones left (victims gone, preemptors nominated, budgets
+//                     and quota lowered), all of it in the call's own buffers.
+//                     k_preempt_blk is k_preempt keeping per-block counts; per
+//                     preemptor only the blocks something changed for
+//                     evaluate again, one wave picks, one wave re-runs the
+//                     chosen node and applies it.
 //
 // Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
 // reads the row the previous add / remove left), so a wave would hold 63 idle
@@ -129,14 +138,26 @@ __device__ __forceinline__ void move_pod(NV &w, QuotaUsed &q, const DevAsg &a, i
   }
 }
 
+// What the sequential dry run lays over one node: the list positions that are
+// gone and the node's nominated preemptors (entries of nom chained from head).
+struct NodeOverlay {
+  uint64_t g0, g1;
+  const NomEntry *nom;
+  int32_t head;
+};
+
+constexpr int EMIT_NONE = 0, EMIT_IDX = 1, EMIT_POS = 2;
+
 // SelectVictimsOnNode of preemptor P on the node whose row is v and whose
-// listed pods are list[0, len).  EMIT: the victims' table indices go to
-// vout[0, vmax) in append order.
-template <bool EMIT>
+// listed pods are list[0, len).  EMIT_IDX: the victims' table indices go to
+// vout[0, vmax) in append order; EMIT_POS: their list positions.  OVL: on the
+// row without the gone pods and with the nominated pods of P's priority and
+// above, over the list without the gone positions.
+template <int EMIT, bool OVL>
 __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
                                                               const NumaRowRS<1> &nr, const DevAsg *__restrict__ list,
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
-                                                              int32_t *vout, int32_t vmax) {
+                                                              int32_t *vout, int32_t vmax, const NodeOverlay &ov) {
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
   if (filter_status(c, pod, v, nr, classes, 0, 0u) & KOORDHIP_ST_STATIC_FAIL) {
@@ -145,6 +166,18 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   }
   const int32_t pprio = P.prio, pquota = P.quota;
   NV w = v;
+  if constexpr (OVL) {
+    for (int h = 0; h < 2; h++) {
+      uint64_t g = h ? ov.g1 : ov.g0;
+      while (g) {
+        const int32_t k = (int32_t)__ffsll((unsigned long long)g) - 1 + 64 * h;
+        g &= g - 1;
+        if (k < len) apply_delta(w, list[k].pod, -1);
+      }
+    }
+    for (int32_t e = ov.head; e >= 0; e = ov.nom[e].next)
+      if (ov.nom[e].prio >= pprio) apply_delta(w, ov.nom[e].pod, +1);
+  }
   QuotaUsed q;
   int32_t pa[KOORDHIP_PREEMPT_PDBS];
 #pragma unroll
@@ -154,6 +187,9 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   // remove every pod canPreempt accepts; the PDB split walks the same pods in the same order
   uint64_t pot0 = 0, pot1 = 0, vio0 = 0, vio1 = 0;
   for (int32_t k = 0; k < len; k++) {
+    if constexpr (OVL) {
+      if (((k < 64 ? ov.g0 : ov.g1) >> (k & 63)) & 1ull) continue;
+    }
     const DevAsg &a = list[k];
     if ((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota) continue;
     move_pod(w, q, a, -1);
@@ -221,8 +257,11 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         es = as;
       }
       sum += (int64_t)ap + (1ll << 31);
-      if constexpr (EMIT) {
+      if constexpr (EMIT == EMIT_IDX) {
         if (nv < vmax) vout[nv] = a.idx;
+      }
+      if constexpr (EMIT == EMIT_POS) {
+        if (nv < vmax) vout[nv] = k;
       }
       nv++;
     }
@@ -252,12 +291,34 @@ __device__ __forceinline__ DevCfg envelope(DevCfg c) {
 // ---------------------------------------------------------------------------
 // k_preempt
 
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                             const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                             const DevPre *__restrict__ pre, int32_t n_pre,
-                                                             int32_t *__restrict__ count,
-                                                             PreemptPartial *__restrict__ part,
-                                                             koordhip_preempt_node *__restrict__ per_node) {
+// the wave's best candidate (r of node bn, -1: none) into every lane
+__device__ __forceinline__ void wave_best(koordhip_preempt_node &r, int32_t &bn) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    koordhip_preempt_node x;
+    x.status = KOORDHIP_PREEMPT_CANDIDATE;
+    x.n_victims = __shfl_xor(r.n_victims, o, 64);
+    x.n_pdb_violations = __shfl_xor(r.n_pdb_violations, o, 64);
+    x.top_priority = __shfl_xor(r.top_priority, o, 64);
+    x.sum_priority = __shfl_xor((long long)r.sum_priority, o, 64);
+    x.earliest_start = __shfl_xor((long long)r.earliest_start, o, 64);
+    const int32_t xn = __shfl_xor(bn, o, 64);
+    if (pick_before(x, xn, r, bn)) {
+      r = x;
+      bn = xn;
+    }
+  }
+}
+
+// BLK: the workgroup's counts go to bcnt [n_pre][gridDim.x][5] instead of
+// being summed into count (the sequential dry run replaces single blocks).
+template <bool BLK>
+__device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
+                                              const int32_t *__restrict__ off, const PdbAllowed &pdb,
+                                              const DevPre *__restrict__ pre, int32_t n_pre,
+                                              int32_t *__restrict__ count, PreemptPartial *__restrict__ part,
+                                              koordhip_preempt_node *__restrict__ per_node,
+                                              int32_t *__restrict__ bcnt) {
   const DevCfg c = envelope(cfg);
   __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
   __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
@@ -283,7 +344,7 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNode
   const DevAsg *list = tab + lo;
   for (int32_t q = 0; q < np; q++) {
     koordhip_preempt_node r{};
-    if (live) r = preempt_node<false>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0);
+    if (live) r = preempt_node<EMIT_NONE, false>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{});
     const int32_t st = live ? r.status : -1;
 #pragma unroll
     for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
@@ -292,21 +353,7 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNode
     }
     if (per_node && live) per_node[(size_t)q * d.n + i] = r;
     int32_t bn = st == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      koordhip_preempt_node x;
-      x.status = KOORDHIP_PREEMPT_CANDIDATE;
-      x.n_victims = __shfl_xor(r.n_victims, o, 64);
-      x.n_pdb_violations = __shfl_xor(r.n_pdb_violations, o, 64);
-      x.top_priority = __shfl_xor(r.top_priority, o, 64);
-      x.sum_priority = __shfl_xor((long long)r.sum_priority, o, 64);
-      x.earliest_start = __shfl_xor((long long)r.earliest_start, o, 64);
-      const int32_t xn = __shfl_xor(bn, o, 64);
-      if (pick_before(x, xn, r, bn)) {
-        r = x;
-        bn = xn;
-      }
-    }
+    wave_best(r, bn);
     if (lane == 0) {
       PreemptPartial b{};
       if (bn >= 0) b.v = r;
@@ -326,8 +373,35 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNode
   }
   for (int32_t w = t; w < np * KOORDHIP_PREEMPT_STATUSES; w += PREEMPT_THREADS) {
     const int32_t x = scnt[w];
-    if (x) atomicAdd(&count[(size_t)p0 * KOORDHIP_PREEMPT_STATUSES + w], x);
+    if constexpr (BLK) {
+      const int32_t q = w / KOORDHIP_PREEMPT_STATUSES, s = w - q * KOORDHIP_PREEMPT_STATUSES;
+      bcnt[((size_t)(p0 + q) * gridDim.x + blockIdx.x) * KOORDHIP_PREEMPT_STATUSES + s] = x;
+    } else {
+      if (x) atomicAdd(&count[(size_t)p0 * KOORDHIP_PREEMPT_STATUSES + w], x);
+    }
   }
+}
+
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                             const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                             const DevPre *__restrict__ pre, int32_t n_pre,
+                                                             int32_t *__restrict__ count,
+                                                             PreemptPartial *__restrict__ part,
+                                                             koordhip_preempt_node *__restrict__ per_node) {
+  preempt_tiles<false>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr);
+}
+
+// Phase 1 of the sequential dry run: one tile of preemptors on the loaded
+// state.  Once the budgets have changed (or with the A/B knob) every block
+// evaluates every later preemptor again and nothing reads this tile: skip it.
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_blk(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                                 const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                 PreemptPartial *__restrict__ part,
+                                                                 int32_t *__restrict__ bcnt,
+                                                                 const StreamFlags *__restrict__ flags) {
+  if (flags->pdb | flags->full) return;
+  preempt_tiles<true>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt);
 }
 
 // one wave per preemptor over its nb partials
@@ -384,7 +458,210 @@ __global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, 
   const int32_t lo = off[i];
   const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
   const DevPre P = pre[p];
-  (void)preempt_node<true>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax);
+  (void)preempt_node<EMIT_IDX, false>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
+                                         NodeOverlay{});
+}
+
+// ---------------------------------------------------------------------------
+// the sequential dry run: preemptor k on the state its predecessors left
+
+__global__ void k_stream_init(PdbAllowed pdb, StreamFlags fl, StreamState st) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    *st.pdb = pdb;
+    *st.flags = fl;
+  }
+}
+
+__device__ __forceinline__ NodeOverlay overlay_of(const StreamState &st, int32_t i) {
+  NodeOverlay ov;
+  ov.g0 = st.gone[2 * (size_t)i];
+  ov.g1 = st.gone[2 * (size_t)i + 1];
+  ov.nom = st.nom;
+  ov.head = st.head[i];
+  return ov;
+}
+
+// preemptor k as it stands now: its quota's used without what its predecessors freed
+__device__ __forceinline__ DevPre stream_pre(const DevPre *__restrict__ pre, const StreamState &st, int32_t k) {
+  DevPre P = pre[k];
+#pragma unroll
+  for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++) {
+    const int64_t f = st.freed[(size_t)k * KOORDHIP_PREEMPT_QRES + r];
+    P.used[r] = P.used[r] > f ? P.used[r] - f : 0;
+  }
+  return P;
+}
+
+// Block b evaluates preemptor k again iff its rows / lists changed, the
+// budgets changed or k's quota was freed; a block none of this holds for keeps
+// the partial and the counts phase 1 wrote (they depend on nothing else).
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off,
+                                                                 const DevPre *__restrict__ pre, int32_t k,
+                                                                 StreamState st) {
+  const int t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
+  const int32_t b = (int32_t)blockIdx.x, nb = (int32_t)gridDim.x;
+  const StreamFlags fl = *st.flags;
+  if (!(fl.full | fl.pdb | st.qflag[k] | st.touched[b])) {
+    if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.stats->blocks_skipped), 1ull);
+    return;
+  }
+  if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.stats->block_recomputes), 1ull);
+  const DevCfg c = envelope(cfg);
+  __shared__ int32_t scnt[KOORDHIP_PREEMPT_STATUSES];
+  __shared__ PreemptPartial sbest[PRE_WAVES];
+  if (t < KOORDHIP_PREEMPT_STATUSES) scnt[t] = 0;
+  __syncthreads();
+  const DevPre P = stream_pre(pre, st, k);
+  const PdbAllowed pdb = *st.pdb;
+  const int32_t i = b * PREEMPT_THREADS + t;
+  const bool live = i < d.n;
+  const int32_t il = live ? i : d.n - 1;
+  NV v{};
+  const Need all = need_all(c);
+  load_node(v, d, il, all, c);
+  NumaRowRS<1> nr{};
+  load_numa<true>(nr, d, il, all);
+  const int32_t lo = off[il];
+  const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+  koordhip_preempt_node r{};
+  if (live)
+    r = preempt_node<EMIT_NONE, true>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, nullptr, 0, overlay_of(st, il));
+  const int32_t s0 = live ? r.status : -1;
+#pragma unroll
+  for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
+    const uint64_t mk = __ballot(s0 == s);
+    if (lane == 0 && mk) atomicAdd(&scnt[s], (int32_t)__popcll(mk));
+  }
+  int32_t bn = s0 == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
+  wave_best(r, bn);
+  if (lane == 0) {
+    PreemptPartial x{};
+    if (bn >= 0) x.v = r;
+    x.node = bn;
+    sbest[wave] = x;
+  }
+  __syncthreads();
+  if (t == 0) {
+    PreemptPartial x = sbest[0];
+#pragma unroll
+    for (int w = 1; w < PRE_WAVES; w++) {
+      const PreemptPartial y = sbest[w];
+      if (pick_before(y.v, y.node, x.v, x.node)) x = y;
+    }
+    st.part[(size_t)k * nb + b] = x;
+  }
+  if (t < KOORDHIP_PREEMPT_STATUSES) st.bcnt[((size_t)k * nb + b) * KOORDHIP_PREEMPT_STATUSES + t] = scnt[t];
+}
+
+// one wave: preemptor k's nb partials and counts -> res[k]
+__global__ __launch_bounds__(64) void k_preempt_seq_pick(int32_t nb, int32_t k, StreamState st) {
+  const int lane = threadIdx.x;
+  PreemptPartial b{};
+  b.node = -1;
+  int32_t cnt[KOORDHIP_PREEMPT_STATUSES] = {};
+  for (int32_t j = lane; j < nb; j += 64) {
+    const PreemptPartial x = st.part[(size_t)k * nb + j];
+    if (pick_before(x.v, x.node, b.v, b.node)) b = x;
+#pragma unroll
+    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++)
+      cnt[s] += st.bcnt[((size_t)k * nb + j) * KOORDHIP_PREEMPT_STATUSES + s];
+  }
+  koordhip_preempt_node r = b.v;
+  int32_t bn = b.node;
+  wave_best(r, bn);
+#pragma unroll
+  for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++)
+    for (int o = 32; o >= 1; o >>= 1) cnt[s] += __shfl_xor(cnt[s], o, 64);
+  if (lane == 0) {
+    koordhip_preempt_result out{};
+    out.node = bn;
+    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) out.count[s] = cnt[s];
+    if (bn >= 0) {
+      out.best = r;
+      out.best.status = KOORDHIP_PREEMPT_CANDIDATE;
+    }
+    st.res[k] = out;
+    if (st.flags->pdb | st.qflag[k]) st.stats->full_recomputes += 1;
+  }
+}
+
+// One wave: the chosen node of preemptor k again, its victims written out and
+// taken off the state every later preemptor sees.
+__global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                      const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
+                                                      int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
+  const DevCfg c = envelope(cfg);
+  const int lane = threadIdx.x;
+  const int32_t i = st.res[k].node;
+  if (i < 0 || i >= d.n) return;
+  const int32_t lo = off[i];
+  const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
+  // the node's list into LDS with the whole wave: lane 0's walk is a chain of dependent loads
+  __shared__ uint4 slist[KOORDHIP_PREEMPT_NODE_PODS * ASG_VEC];
+  const uint4 *src = reinterpret_cast<const uint4 *>(tab + lo);
+  for (int32_t w = lane; w < len * ASG_VEC; w += 64) slist[w] = src[w];
+  __syncthreads();
+  const DevAsg *list = reinterpret_cast<const DevAsg *>(slist);
+  const DevPre P = stream_pre(pre, st, k);
+  __shared__ int32_t sfreed;
+  __shared__ int64_t ssum[KOORDHIP_PREEMPT_QRES];
+  if (lane == 0) {
+    NV v{};
+    const Need all = need_all(c);
+    load_node(v, d, i, all, c);
+    NumaRowRS<1> nr{};
+    load_numa<true>(nr, d, i, all);
+    PdbAllowed pdb = *st.pdb;
+    const koordhip_preempt_node r = preempt_node<EMIT_POS, true>(c, d.nu.cls, v, nr, list, len, pdb, P, st.vpos,
+                                                                 KOORDHIP_PREEMPT_NODE_PODS, overlay_of(st, i));
+    const int32_t nv = r.status == KOORDHIP_PREEMPT_CANDIDATE ? min(r.n_victims, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+    uint64_t g0 = 0, g1 = 0;
+    int64_t sum[KOORDHIP_PREEMPT_QRES] = {};
+    bool moved = false;
+    for (int32_t e = 0; e < nv; e++) {
+      const int32_t pos = st.vpos[e];
+      const DevAsg &a = list[pos];
+      if (st.victims && e < vmax) st.victims[(size_t)k * vmax + e] = a.idx;
+      if (pos < 64) g0 |= 1ull << pos; else g1 |= 1ull << (pos - 64);
+      const uint32_t pm = a.pdb_mask;
+      for (int bb = 0; bb < KOORDHIP_PREEMPT_PDBS; bb++)
+        if (((pm >> bb) & 1u) && pdb.a[bb] > 0) {
+          pdb.a[bb]--;
+          moved = true;
+        }
+      if (a.flags & KOORDHIP_ASG_IN_QUOTA)
+        for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) sum[q] += a.qreq[q];
+    }
+    st.gone[2 * (size_t)i] |= g0;
+    st.gone[2 * (size_t)i + 1] |= g1;
+    NomEntry ne;
+    ne.pod = P.pod;
+    ne.prio = P.prio;
+    ne.next = st.head[i];
+    st.nom[k] = ne;
+    st.head[i] = k;
+    st.touched[i / PREEMPT_THREADS] = 1;
+    if (moved) {
+      *st.pdb = pdb;
+      st.flags->pdb = 1;
+    }
+    int64_t any = 0;
+    for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) {
+      ssum[q] = sum[q];
+      any |= sum[q];
+    }
+    sfreed = any != 0;
+  }
+  __syncthreads();
+  // what the victims held in k's quota is free for every later preemptor of that quota
+  const int32_t quota = P.quota;
+  if (quota < 0 || !sfreed) return;
+  for (int32_t j = k + 1 + lane; j < n_pre; j += 64) {
+    if (pre[j].quota != quota) continue;
+    for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) st.freed[(size_t)j * KOORDHIP_PREEMPT_QRES + q] += ssum[q];
+    st.qflag[j] = 1;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -419,6 +696,29 @@ hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab,
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_preempt, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node);
+  return hipGetLastError();
+}
+
+hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                                 const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
+                                 int32_t max_victims, bool full, hipStream_t s) {
+  if (n_pre <= 0 || d.n <= 0) return hipSuccess;
+  if (c.resv || (c.filt & (KOORDHIP_PLUGIN_NUMA | KOORDHIP_PLUGIN_RESERVATION))) return hipErrorInvalidValue;
+  const int32_t nb = preempt_blocks(d.n);
+  StreamFlags fl{};
+  fl.full = full ? 1 : 0;
+  hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, s, pdb, fl, st);
+  for (int32_t k = 0; k < n_pre; k++) {
+    // phase 1 a tile ahead of its first preemptor, not all at once: the loaded state does not change, and a tile
+    // launched after the budgets changed costs an empty kernel
+    if (k % PRE_PT == 0)
+      hipLaunchKernelGGL(k_preempt_blk, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
+                         std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
+                         st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags);
+    hipLaunchKernelGGL(k_preempt_seq, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st);
+    hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), dim3(64), 0, s, nb, k, st);
+    hipLaunchKernelGGL(k_preempt_apply, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
+  }
   return hipGetLastError();
 }
 

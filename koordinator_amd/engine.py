@@ -292,6 +292,23 @@ class PlacementEngine:
                                                       abi.ptr(vic, C.c_int32) if max_victims else None, max_victims))
         return out, vic
 
+    def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0):
+        """The dry run of a batch whose answers hold together: the preemptors
+        are processed in input order, each on the state the earlier ones left
+        (their victims gone, they themselves nominated on their nodes, PDB
+        budgets and their quotas' used lowered; include/koordhip.h).  Every
+        q_used is as of the start of the call.  Returns (results, victims,
+        stats) with stats a dict of koordhip_preempt_stream_stats.  Writes no
+        engine state and leaves the loaded table as it was."""
+        pre = np.ascontiguousarray(np.atleast_1d(preemptors), dtype=abi.PREEMPTOR_DTYPE)
+        out = np.zeros(len(pre), abi.PREEMPT_RESULT_DTYPE)
+        vic = np.full((len(pre), max_victims), -1, np.int32)
+        st = np.zeros(1, abi.PREEMPT_STREAM_STATS_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_preempt_stream(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
+                                                             abi.ptr(vic, C.c_int32) if max_victims else None,
+                                                             max_victims, st.ctypes.data))
+        return out, vic, {f: int(st[f][0]) for f in st.dtype.names}
+
     def preempt_node_verdicts(self, preemptor) -> np.ndarray:
         """One preemptor's verdict on every node (abi.PREEMPT_NODE_DTYPE [n])."""
         pre = np.ascontiguousarray(np.atleast_1d(preemptor), dtype=abi.PREEMPTOR_DTYPE)

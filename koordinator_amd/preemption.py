@@ -8,6 +8,14 @@ pods that sit on the nodes, the preemptor records and a view of the result.
     PreemptionResult   node name + victim pod keys of one preemptor
 
 PodEligibleToPreemptOthers and nominated pods stay with the caller.
+
+For a batch answered by PlacementEngine.preempt_stream (koordhip_preempt_stream)
+the records are the same, and every QuotaState.used is the quota's used AS OF
+THE START OF THE CALL: the engine itself lowers it for a later preemptor of the
+same quota by what the earlier preemptors' victims held (floored at 0), and it
+does not add the nominated preemptors to it.  Do not pre-subtract victims of
+preemptors of the same batch, and do not reuse the records of one call for the
+next without refreshing used, the table and the PDBs' DisruptionsAllowed.
 """
 from __future__ import annotations
 
