@@ -45,7 +45,9 @@ def nblocks(m):
 # ------------------------------------------------------ 1. results and victims
 @pytest.mark.parametrize("name", S.CASES)
 def test_stream_results_and_victims(Engine, name):
-    """The six cases of the independent dry run, `clean` and `prio`; victims at
+    """The six cases of the independent dry run, `clean`, `prio` and the
+    directed cases (the second overlay word, a chain of nominated pods, a spent
+    budget, a floored quota, three phase-1 tiles); victims at
     max_victims 0, exact and truncated.  The later calls run in the same
     context: the call's own state is set up anew every time."""
     m = S.case(name)
@@ -72,7 +74,7 @@ def test_truncation_is_exercised():
 
 
 # ------------------------------------------------------------ 2. A/B and stats
-@pytest.mark.parametrize("name", ["tiles", "clean", "prio", "la257"])
+@pytest.mark.parametrize("name", ["tiles", "clean", "prio", "la257"] + list(S.DIRECTED))
 def test_full_recompute_gives_the_same_answers(Engine, name, monkeypatch):
     """KOORDHIP_PREEMPT_STREAM_FULL is read at every call, so both runs share
     this process; each gets a fresh context."""

@@ -1,8 +1,10 @@
-"""The preemption model (preempt_model.py) itself: hand-worked one- and
-two-node cases with the expected verdicts written out, the generated cases'
-inputs (no degenerate case: candidates, nodes without victims, unfit nodes and
-reprieved pods all occur), and the byte layout of the three new ABI structs
-against gcc's view of the header.  No GPU."""
+"""The preemption model (preempt_model.py) itself: the hand-worked one- and
+two-node cases of preempt_cases.py with the expected verdicts written out
+(here again, and there in full), the construction of the contest cluster the
+device's pick runs on (every contest's key level, placement and answer), the
+generated cases' inputs (no degenerate case: candidates, nodes without
+victims, unfit nodes and reprieved pods all occur), and the byte layout of the
+three new ABI structs against gcc's view of the header.  No GPU."""
 import os
 import subprocess
 import tempfile
@@ -11,192 +13,262 @@ import numpy as np
 import pytest
 
 from koordinator_amd import abi
-from koordinator_amd.config import PLUGIN_FIT, Profile, to_c_config, with_upstream
-from koordinator_amd.snapshot import NodeTable
 
+import preempt_cases as K
 import preempt_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CAND, NOV, UNFIT, ERR, UNRES = range(5)
-B = 1 << 31
-ALLOC = 10000
+CAND, NOV, UNFIT, ERR, UNRES, B, ZERO = K.CAND, K.NOV, K.UNFIT, K.ERR, K.UNRES, K.B, K.ZERO
 
 
-def A(node, cpu, prio, start=0, quota=0, flags=abi.ASG_IN_QUOTA, pdb=0):
-    """One assigned pod requesting `cpu` milli-CPU."""
-    a = np.zeros((), abi.ASSIGNED_DTYPE)
-    a["pod"]["req"][abi.RES_CPU] = a["pod"]["nz_cpu_m"] = a["qreq"][0] = cpu
-    a["pod"]["flags"] = abi.POD_HAS_REQ
-    a["node"], a["priority"], a["start_time"], a["quota"], a["flags"], a["pdb_mask"] = node, prio, start, quota, flags, pdb
-    return a
+def run(case):
+    """The model on a hand-worked case, and the case's whole expectation against it."""
+    ver, vic, res = K.run_case(case)
+    assert ver == case.ver
+    assert vic == case.vic
+    assert int(res["node"]) == case.node and list(res["count"]) == case.count
+    assert tuple(res["best"].item()) == case.best
+    return ver, vic, res
 
 
-def preemptor(cpu, prio=1000, quota=0, used=0, runtime=None):
-    p = np.zeros((), abi.PREEMPTOR_DTYPE)
-    p["pod"]["req"][abi.RES_CPU] = p["pod"]["nz_cpu_m"] = p["q_req"][0] = cpu
-    p["pod"]["flags"] = abi.POD_HAS_REQ
-    p["priority"], p["quota"], p["q_used"][0] = prio, quota, used
-    if runtime is not None:
-        p["q_mask"], p["q_runtime"][0] = 1, runtime
-    return p
-
-
-def run(n, pods, pre, pdb=(), extra=None, static_off=()):
-    """Nodes of 10 CPUs whose Requested is their pods' (plus extra[i]); returns
-    (verdicts as tuples, victims per node, the pick)."""
-    prof = Profile(filters=(PLUGIN_FIT,), scores={PLUGIN_FIT: 1})
-    if static_off:
-        prof = with_upstream(prof)
-    t = NodeTable.empty(n)
-    t["alloc0"][:] = ALLOC
-    t["alloc1"][:] = 1 << 40
-    t["alloc_pods"][:] = 110
-    a = np.array(pods, abi.ASSIGNED_DTYPE) if pods else np.zeros(0, abi.ASSIGNED_DTYPE)
-    for x in a:
-        t["requested0"][x["node"]] += x["pod"]["req"][abi.RES_CPU]
-        t["nz_cpu_m"][x["node"]] += x["pod"]["nz_cpu_m"]
-        t["npods"][x["node"]] += 1
-    for i, e in enumerate(extra or ()):
-        t["requested0"][i] += e
-    for i in static_off:
-        t["static_allow"][i] = 0
-    ver, vic, _ = M.select_victims(to_c_config(prof), t, a, pdb, pre)
-    return [tuple(int(x) for x in v) for v in ver], vic, M.pick(ver)
-
-
-ZERO = (0, 0, 0, 0, 0)
+@pytest.mark.parametrize("name", list(K.WALK) + list(K.PICK) + list(K.EXTREME))
+def test_hand_worked_case(name):
+    run({**K.WALK, **K.PICK, **K.EXTREME}[name])
 
 
 def test_candidate_with_a_reprieved_pod():
-    # free 0; without a0 and a1 5 CPUs are free; a0 back leaves 2 (< 3): victim; a1 back leaves 3: reprieved
-    ver, vic, res = run(1, [A(0, 3000, 100, 10), A(0, 2000, 50, 20), A(0, 4000, 2000, 5)], preemptor(3000), extra=[1000])
+    ver, vic, res = run(K.WALK["reprieved"])
     assert ver == [(CAND, 1, 0, 100, 100 + B, 10)]
     assert vic == [[0]]
     assert int(res["node"]) == 0 and list(res["count"]) == [1, 0, 0, 0, 0]
 
 
 def test_no_victims():
-    # a higher priority, another quota, a non-preemptible pod: canPreempt accepts none
-    pods = [A(0, 3000, 2000), A(0, 3000, 10, quota=1), A(0, 3000, 10, flags=abi.ASG_NONPREEMPTIBLE)]
-    ver, vic, res = run(1, pods, preemptor(3000))
+    ver, vic, res = run(K.WALK["no_victims"])
     assert ver == [(NOV,) + ZERO]
     assert int(res["node"]) == -1 and list(res["count"]) == [0, 1, 0, 0, 0]
-    # postFilterState.skip: the ids still differ
-    ver, _, _ = run(1, [A(0, 3000, 10)], preemptor(3000, quota=-1))
+    ver, _, _ = run(K.WALK["no_victims_skip"])
     assert ver == [(NOV,) + ZERO]
-    # equal priority is not lower
-    ver, _, _ = run(1, [A(0, 3000, 1000)], preemptor(3000, prio=1000))
+    ver, _, _ = run(K.WALK["no_victims_equal_priority"])
     assert ver == [(NOV,) + ZERO]
 
 
 def test_unfit():
-    ver, _, res = run(1, [A(0, 500, 0)], preemptor(3000), extra=[9500])
+    ver, _, res = run(K.WALK["unfit"])
     assert ver == [(UNFIT,) + ZERO]
     assert list(res["count"]) == [0, 0, 1, 0, 0]
 
 
 def test_unresolvable():
-    pods = [A(0, 3000, 10), A(1, 3000, 10)]
-    ver, _, res = run(2, pods, preemptor(3000), extra=[7000, 7000], static_off=[0])
+    ver, _, res = run(K.WALK["unresolvable"])
     assert ver == [(UNRES,) + ZERO, (CAND, 1, 0, 10, 10 + B, 0)]
     assert int(res["node"]) == 1 and list(res["count"]) == [1, 0, 0, 0, 1]
 
 
 def test_error_a_pod_removed_twice():
-    # a0 does not fit back (removed once) and used 0 + 3000 > runtime 2000 (removed again): RemovePod fails
-    pods = [A(0, 3000, 100), A(0, 2000, 50)]
-    ver, vic, res = run(1, pods, preemptor(3000, used=5000, runtime=2000), extra=[5000])
+    ver, vic, res = run(K.WALK["error"])
     assert ver == [(ERR,) + ZERO]
     assert vic == [[]]
     assert int(res["node"]) == -1 and list(res["count"]) == [0, 0, 0, 1, 0]
 
 
 def test_victim_by_quota_alone():
-    # both fit back (5 CPUs free without them, the preemptor asks 2); with a0 back used 3000 + 2000 > 4500
-    pods = [A(0, 3000, 100, 7), A(0, 2000, 50, 9)]
-    ver, vic, _ = run(1, pods, preemptor(2000, used=5000, runtime=4500), extra=[5000])
+    ver, vic, _ = run(K.WALK["quota_alone"])
     assert ver == [(CAND, 1, 0, 100, 100 + B, 7)]
     assert vic == [[0]]
-    # a pod the quota does not count moves no `used`: with runtime 1999 every pod is over, none is reprieved
-    pods = [A(0, 3000, 100, 7, flags=0), A(0, 2000, 50, 9)]
-    ver, vic, _ = run(1, pods, preemptor(2000, used=2000, runtime=1999), extra=[5000])
+    ver, vic, _ = run(K.WALK["quota_alone_uncounted"])
     assert ver == [(CAND, 2, 0, 100, 150 + 2 * B, 7)]
     assert vic == [[0, 1]]
 
 
 def test_pdb_budget_zero_counts_a_violation():
-    ver, vic, _ = run(1, [A(0, 3000, 100, 3, pdb=1)], preemptor(3000), pdb=(0,), extra=[7000])
+    ver, vic, _ = run(K.WALK["pdb_zero"])
     assert ver == [(CAND, 1, 1, 100, 100 + B, 3)]
-    # budget 1: the first matching pod is within it, the second violates; a reprieved violating pod counts nothing
-    pods = [A(0, 3000, 100, 3, pdb=1), A(0, 1000, 50, 4, pdb=1)]
-    ver, vic, _ = run(1, pods, preemptor(3000), pdb=(1,), extra=[6000])
+    ver, vic, _ = run(K.WALK["pdb_one"])
     assert vic == [[0]]                     # a1 (violating) goes first and fits back; a0 does not
     assert ver == [(CAND, 1, 0, 100, 100 + B, 3)]
 
 
 def test_violating_pod_of_lower_priority_is_listed_first():
-    pods = [A(0, 3000, 100, 5), A(0, 2000, 50, 6, pdb=1)]
-    # 5 CPUs free without them, the preemptor asks 4: neither fits back
-    ver, vic, _ = run(1, pods, preemptor(4000), pdb=(0,), extra=[5000])
+    ver, vic, _ = run(K.WALK["violating_first"])
     assert vic == [[1, 0]]
     assert ver == [(CAND, 2, 1, 50, 150 + 2 * B, 5)]   # top_priority 50, not the maximum 100
 
 
 def test_list_order_ties():
-    # equal priority: the earlier start first; equal start too: the lower input index first
-    pods = [A(0, 1000, 7, 30), A(0, 1000, 7, 20), A(0, 1000, 7, 20), A(0, 1000, 9, 40)]
-    assert M.node_lists(np.array(pods, abi.ASSIGNED_DTYPE), 1) == [[3, 1, 2, 0]]
-    _, vic, _ = run(1, pods, preemptor(ALLOC))   # the preemptor asks the whole node: all victims, in that order
+    case = K.WALK["list_order"]
+    assert M.node_lists(case.assigned, 1) == [[3, 1, 2, 0]] == case.lists
+    _, vic, _ = run(case)
     assert vic == [[3, 1, 2, 0]]
 
 
-# every pod of these nodes becomes a victim: the preemptor asks the whole node
-def two_nodes(pods, pdb=()):
-    ver, vic, res = run(2, pods, preemptor(ALLOC, prio=1 << 30), pdb=pdb)
+def two_nodes(name):
+    ver, _, res = run(K.PICK[name])
     assert [v[0] for v in ver] == [CAND, CAND]
     return ver, int(res["node"]), res
 
 
 def test_pick_by_pdb_violations():
-    ver, node, _ = two_nodes([A(0, 1000, 100, pdb=1), A(1, 1000, 100)], pdb=(0,))
+    ver, node, _ = two_nodes("pdb")
     assert (ver[0][2], ver[1][2]) == (1, 0) and node == 1
 
 
 def test_pick_by_top_priority():
-    ver, node, _ = two_nodes([A(0, 1000, 200), A(1, 1000, 100), A(1, 1000, 100)])
+    ver, node, _ = two_nodes("top")
     assert (ver[0][3], ver[1][3]) == (200, 100) and node == 1
 
 
 def test_pick_by_sum_priority():
-    ver, node, _ = two_nodes([A(0, 1000, 100), A(0, 1000, 100), A(1, 1000, 100), A(1, 1000, 50)])
+    ver, node, _ = two_nodes("sum")
     assert ver[0][3] == ver[1][3] and ver[0][4] > ver[1][4] and node == 1
 
 
 def test_pick_by_victim_count():
-    # a victim of priority -2^31 adds 0 to the sum: equal sums, three victims against two
-    lo = -(1 << 31)
-    ver, node, _ = two_nodes([A(0, 1000, 0), A(0, 1000, 0), A(0, 1000, lo), A(1, 1000, 0), A(1, 1000, 0)])
+    ver, node, _ = two_nodes("count")
     assert ver[0][2:5] == ver[1][2:5] and (ver[0][1], ver[1][1]) == (3, 2) and node == 1
 
 
 def test_pick_by_latest_start():
-    ver, node, _ = two_nodes([A(0, 1000, 100, 10), A(0, 1000, 50, 99), A(1, 1000, 100, 20), A(1, 1000, 50, 1)])
+    ver, node, _ = two_nodes("start")
     assert ver[0][1:5] == ver[1][1:5] and (ver[0][5], ver[1][5]) == (10, 20) and node == 1
 
 
 def test_pick_by_node_index():
-    ver, node, res = two_nodes([A(0, 1000, 100, 10), A(1, 1000, 100, 10)])
+    ver, node, res = two_nodes("index")
     assert ver[0] == ver[1] and node == 0
     assert tuple(res["best"].item()) == ver[0]
 
 
 def test_a_candidate_without_victims_wins_outright():
-    # node 0: one victim of priority -5, the smaller key field by field; node 1: the preemptor fits with its pod back
-    pods = [A(0, 3000, -5), A(1, 1000, 10)]
-    ver, vic, res = run(2, pods, preemptor(3000), extra=[7000, 6000])
+    ver, vic, res = run(K.PICK["zero"])
     assert ver == [(CAND, 1, 0, -5, -5 + B, 0), (CAND,) + ZERO]
     assert vic == [[0], []]
     assert int(res["node"]) == 1 and int(res["best"]["n_victims"]) == 0
+
+
+def test_three_equal_candidates():
+    run(K.THREE)
+
+
+# ------------------------------------------------------- the contest cluster
+@pytest.fixture(scope="module")
+def cluster():
+    return K.contest_cluster()
+
+
+def test_each_level_is_the_first_at_which_its_contest_differs():
+    """What keeps the device test honest: the contest named for a level is decided there and nowhere before."""
+    assert list(K.LEVELS.values()) == list(range(7))
+    for name, level in K.LEVELS.items():
+        assert K.first_difference(K.PICK[name]) == level, name
+    for name, level in K.EXTREME_LEVEL.items():
+        assert K.first_difference(K.EXTREME[name]) == level, name
+    assert set(K.EXTREME_LEVEL) == set(K.EXTREME)
+    # the halves: which 32 bits of the deciding field differ
+    def halves(name, field):
+        x, y = (v[field] & ((1 << 64) - 1) for v in K.EXTREME[name].ver)
+        return (x >> 32) != (y >> 32), (x & 0xFFFFFFFF) != (y & 0xFFFFFFFF)
+    assert halves("start_high_half", 5) == (True, False) and halves("start_low_half", 5) == (False, True)
+    assert halves("sum_high_half", 4) == (True, False) and halves("sum_low_half", 4) == (False, True)
+    for name, field in (("start_halves_disagree", 5), ("sum_halves_disagree", 4)):
+        x, y = (v[field] for v in K.EXTREME[name].ver)
+        assert (x < y) != ((x & 0xFFFFFFFF) < (y & 0xFFFFFFFF)), name
+    # with the high word of the sums lost the next level (fewer victims) would pick the other node
+    v = K.EXTREME["sum_high_half"].ver
+    assert v[1][4] < v[0][4] and v[1][1] > v[0][1]
+    assert {K.EXTREME["start_min_max"].ver[i][5] for i in (0, 1)} == {K.I64_MIN, K.I64_MAX}
+    assert K.EXTREME["start_sign"].ver[0][5] < 0 <= K.EXTREME["start_sign"].ver[1][5]
+    assert {K.EXTREME["top_lowest"].ver[i][3] for i in (0, 1)} == {K.LO, K.LO + 1}
+    assert {K.EXTREME["top_highest"].ver[i][3] for i in (0, 1)} == {(1 << 30) - 1, (1 << 30) - 2}
+
+
+def test_contests_cover_levels_placements_and_orientations(cluster):
+    n, cts = K.CLUSTER_N, cluster.contests
+    assert n == 65 * 256 + 1 and (n + 255) // 256 == K.CLUSTER_BLOCKS == 66
+    assert len(cts) == len(cluster.pres) == 116 and len(cts) % 32 != 0 and (len(cts) + 31) // 32 == 4
+    names = {ct.name for ct in cts}
+    assert len(names) == len(cts)
+    for placement in K.PLACEMENTS:
+        for level in K.LEVELS:
+            assert {f"{level}/{placement}/lo", f"{level}/{placement}/hi"} <= names
+    for placement in ("wave", "far"):
+        for name in K.EXTREME:
+            assert {f"{name}/{placement}/lo", f"{name}/{placement}/hi"} <= names
+    assert {"start/ragged/hi", "three"} <= names
+    # the node sets are disjoint, and so are the quotas
+    used = [i for ct in cts for i in ct.nodes]
+    assert len(used) == len(set(used)) and 0 <= min(used) and max(used) == n - 1
+    assert [ct.quota for ct in cts] == list(range(len(cts)))
+    assert (cluster.pres["quota"] == np.arange(len(cts))).all() and (cluster.pres["q_mask"] == 0).all()
+    for ct in cts:
+        own = cluster.assigned[ct.base:ct.base + len(ct.case.pods)]
+        assert (own["quota"] == ct.quota).all() and set(own["node"].tolist()) <= set(ct.nodes)
+        assert ((own["pdb_mask"] != 0).any()) == ct.name.startswith("pdb/")
+    # the placements straddle what they are named for
+    every = set(K.PLACEMENTS) | {"ragged", "three"}
+    assert {ct.placement for ct in cts} == every
+    for ct in cts:
+        i, j = sorted(ct.nodes)[:2]
+        wave, group = (i // 64, j // 64), (i // 256, j // 256)
+        if ct.placement == "wave":
+            assert wave[0] == wave[1]
+        elif ct.placement == "lanes":
+            assert (i % 64, j) == (63, i + 1) and group[0] == group[1]
+        elif ct.placement == "groups":
+            assert (i % 256, j) == (255, i + 1)
+        elif ct.placement == "strided":
+            assert group[1] == group[0] + 64          # the same lane of the pick, the loop's next trip
+        elif ct.placement == "far":
+            assert group == (1, 33)                   # lanes 1 and 33 differ in bit 5 alone: shuffle offset 32
+        elif ct.placement == "ragged":
+            assert group == (0, 65) and j == n - 1 and ct.node == j
+        else:
+            assert len({x // 256 for x in ct.nodes}) == 3 and ct.node == min(ct.nodes)
+    # orientation: the better node at the lower and at the higher index; equal keys: the lower index wins
+    for ct in cts:
+        if ct.name.startswith("index/"):
+            assert ct.node == min(ct.nodes), ct.name
+        elif ct.name.endswith("/lo"):
+            assert ct.node == min(ct.nodes), ct.name
+        elif ct.name.endswith("/hi"):
+            assert ct.node == max(ct.nodes), ct.name
+
+
+def test_every_contests_two_node_reduction(cluster):
+    """Each contest alone, on as many nodes as it has, in the orientation it has in the cluster."""
+    for ct in cluster.contests:
+        order = np.argsort(ct.nodes)                  # local node k of this run = the contest's k-th lowest node
+        local = {int(ct.nodes[c]): k for k, c in enumerate(order)}
+        sel = slice(ct.base, ct.base + len(ct.case.pods))
+        pods = cluster.assigned[sel].copy()
+        pods["node"] = [local[int(x)] for x in pods["node"]]
+        t = K.table(ct.case.n, pods)
+        for node, k in local.items():
+            t["requested0"][k] = cluster.table["requested0"][node]
+        ver, vic, _ = M.select_victims(cluster.cfg, t, pods, cluster.pdb_allowed, cluster.pres[ct.quota])
+        res = M.pick(ver)
+        assert int(res["node"]) == local[ct.node], ct.name
+        assert tuple(res["best"].item()) == tuple(ct.best), ct.name
+        assert [ct.base + j for j in vic[int(res["node"])]] == ct.victims, ct.name
+        assert list(res["count"]) == [ct.case.n, 0, 0, 0, 0], ct.name
+
+
+def test_full_cluster_for_one_contest_per_placement(cluster):
+    """The model on all 16641 nodes: the contest's own nodes are the only candidates."""
+    lists = M.node_lists(cluster.assigned, K.CLUSTER_N)
+    want = ["start/wave/hi", "index/lanes/lo", "count/groups/lo", "zero/strided/hi", "pdb/far/lo", "start/ragged/hi",
+            "three", "sum_high_half/far/hi"]
+    by_name = {ct.name: ct for ct in cluster.contests}
+    for name in want:
+        ct = by_name[name]
+        ver, vic, _ = M.select_victims(cluster.cfg, cluster.table, cluster.assigned, cluster.pdb_allowed,
+                                       cluster.pres[ct.quota], lists)
+        res = M.pick(ver)
+        assert res.tobytes() == cluster.res[ct.quota].tobytes(), name
+        assert list(res["count"]) == [ct.case.n, K.CLUSTER_N - ct.case.n, 0, 0, 0], name
+        assert sorted(np.flatnonzero(ver["status"] == abi.PREEMPT_CANDIDATE).tolist()) == sorted(ct.nodes), name
+        assert vic[ct.node] == ct.victims, name
+    assert cluster.victims.shape == (len(cluster.pres), 4)
 
 
 def test_victims_array_pads_and_truncates():

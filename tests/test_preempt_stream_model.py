@@ -2,7 +2,8 @@
 one- and two-node cases with the expected answers written out, the conditions
 that keep the generated cases from being degenerate (the stream really differs
 from the independent batch, no pod is a victim twice, both kinds of global
-flag rise in `tiles` and none in `clean`), and the byte layout of
+flag rise in `tiles` and none in `clean`), that every directed case reaches
+the situation it is named for, and the byte layout of
 koordhip_preempt_stream_stats against gcc's view of the header.  No GPU."""
 import os
 import subprocess
@@ -18,30 +19,12 @@ from koordinator_amd.snapshot import NodeTable
 
 import preempt_model as M
 import preempt_stream_model as S
+from preempt_cases import A, preemptor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAND, NOV, UNFIT, ERR, UNRES = range(5)
 B = 1 << 31
 ALLOC = 10000
-
-
-def A(node, cpu, prio, start=0, quota=0, flags=abi.ASG_IN_QUOTA, pdb=0):
-    """One assigned pod requesting `cpu` milli-CPU."""
-    a = np.zeros((), abi.ASSIGNED_DTYPE)
-    a["pod"]["req"][abi.RES_CPU] = a["pod"]["nz_cpu_m"] = a["qreq"][0] = cpu
-    a["pod"]["flags"] = abi.POD_HAS_REQ
-    a["node"], a["priority"], a["start_time"], a["quota"], a["flags"], a["pdb_mask"] = node, prio, start, quota, flags, pdb
-    return a
-
-
-def preemptor(cpu, prio=1000, quota=0, used=0, runtime=None):
-    p = np.zeros((), abi.PREEMPTOR_DTYPE)
-    p["pod"]["req"][abi.RES_CPU] = p["pod"]["nz_cpu_m"] = p["q_req"][0] = cpu
-    p["pod"]["flags"] = abi.POD_HAS_REQ
-    p["priority"], p["quota"], p["q_used"][0] = prio, quota, used
-    if runtime is not None:
-        p["q_mask"], p["q_runtime"][0] = 1, runtime
-    return p
 
 
 def setup(n, pods, extra):
@@ -149,6 +132,115 @@ def test_prio_case_is_what_its_docstring_says():
     assert list(m.res["count"][2]) == [1, 2, 0, 0, 0]
     # were the nominated pod of priority 100 counted for the preemptor of priority 1000, node 1 would be UNFIT
     assert list(m.res["count"][1]) == [2, 0, 1, 0, 0]
+
+
+# --------------------------------------------------------- the directed cases
+def alone(m, k):
+    """Preemptor k of the case on the loaded state, as koordhip_preempt answers it."""
+    return M.select_victims(m.cfg, m.table, m.assigned, m.pdb_allowed, m.pres[k])
+
+
+def test_word1_reads_the_second_overlay_word():
+    m = S.case("word1")
+    assert int((m.assigned["node"] == 0).sum()) == abi.PREEMPT_NODE_PODS
+    assert m.res["node"].tolist() == [0, 0, 0]
+    pos = {j: k for k, j in enumerate(M.node_lists(m.assigned, 2)[0])}
+    first = sorted(pos[j] for j in m.chosen[0])
+    assert first == list(range(58, 128))            # 6 positions of the first word, all 64 of the second
+    # the later preemptors of the same quota walk the same list without them
+    assert sorted(pos[j] for j in m.chosen[1]) == list(range(48, 58))
+    assert sorted(pos[j] for j in m.chosen[2]) == list(range(38, 48))
+    assert len({int(q) for q in m.pres["quota"]}) == 1
+    assert [best(r) for r in m.res] == [(CAND, 70, 0, 386, 70 * B + sum(400 - p // 4 for p in range(58, 128)), 2),
+                                        (CAND, 10, 0, 388, 10 * B + sum(400 - p // 4 for p in range(48, 58)), 0),
+                                        (CAND, 10, 0, 391, 10 * B + sum(400 - p // 4 for p in range(38, 48)), 2)]
+    assert m.res["count"].tolist() == [[1, 0, 1, 0, 0], [2, 0, 0, 0, 0], [1, 0, 1, 0, 0]]
+    # the input order is not the list's
+    assert [pos[j] for j in range(4)] == [0, 37, 74, 111]
+
+
+def test_chain_of_nominated_pods_straddles_the_last_priority():
+    m = S.case("chain")
+    assert m.res["node"].tolist() == [0, 0, 0, 0, 0]     # four nominated on node 0 before the fifth looks at it
+    prio = [int(p) for p in m.pres["priority"]]
+    assert prio == list(S.CHAIN_PRIORITIES)
+    assert sorted(p >= prio[4] for p in prio[:4]) == [False, False, True, True]
+    assert m.chosen == [[0], [1], [2], [4, 3], [5]]
+    assert [best(r) for r in m.res] == [(CAND, 1, 0, 1, 1 + B, 1), (CAND, 1, 0, 2, 2 + B, 2), (CAND, 1, 0, 3, 3 + B, 3),
+                                        (CAND, 2, 0, 5, 9 + 2 * B, 5), (CAND, 1, 0, 6, 6 + B, 6)]
+    assert m.res["count"].tolist() == [[2, 0, 0, 0, 0]] * 3 + [[1, 1, 0, 0, 0], [2, 0, 0, 0, 0]]
+    # alone, the fifth would take the three pods of the lowest priorities
+    ver, vic, _ = alone(m, 4)
+    assert vic[0] == [2, 1, 0]
+
+
+def test_budget_is_spent_once_and_stays_at_zero():
+    m = S.case("budget")
+    assert m.pdb_allowed == (1,)
+    assert m.res["node"].tolist() == [0, 3, 1, 2] and m.chosen == [[0], [3], [1], [2]]
+    npdb = [best(r)[2] for r in m.res]
+    assert npdb == [0, 0, 1, 1]                          # a violation after a 0 before
+    assert m.stats["pdb_flag"]
+    assert [int(m.assigned["pdb_mask"][v[0]]) for v in m.chosen] == [1, 0, 1, 1]   # two more matching victims at 0
+    assert [best(r) for r in m.res] == [(CAND, 1, 0, 10, 10 + B, 0), (CAND, 1, 0, 500, 500 + B, 0),
+                                        (CAND, 1, 1, 20, 20 + B, 0), (CAND, 1, 1, 30, 30 + B, 0)]
+    assert m.res["count"].tolist() == [[4, 0, 0, 0, 0], [3, 1, 0, 0, 0], [2, 2, 0, 0, 0], [1, 3, 0, 0, 0]]
+    # alone every one of them takes node 0 within the budget
+    ind = M.dry_run(m.cfg, m.table, m.assigned, m.pdb_allowed, m.pres)[0]
+    assert ind["node"].tolist() == [0] * 4 and not ind["best"]["n_pdb_violations"].any()
+
+
+def test_quota_used_is_floored_at_zero():
+    m = S.case("floor")
+    assert m.res["node"].tolist() == [0, 1, -1] and m.chosen == [[0], [1], []]
+    freed = int(m.assigned["qreq"][0][0])
+    assert freed > int(m.pres["q_used"][1][0]) == int(m.pres["q_used"][2][0]) > 0     # more freed than used
+    # preemptor 1 alone: both pods of node 1 are victims, neither because it does not fit back
+    ver, vic, _ = alone(m, 1)
+    assert vic[1] == [2, 1] and best_of(ver[1]) == (CAND, 2, 0, 45, 85 + 2 * B, 0)
+    ample = m.pres[1].copy()
+    ample["q_runtime"][0] = 1 << 40
+    assert alone_with(m, ample)[1][1] == [1]             # by fit the pod of 40 alone
+    # in sequence: one victim, and that one by fit
+    assert best(m.res[1]) == (CAND, 1, 0, 40, 40 + B, 0) and list(m.res["count"][1]) == [1, 1, 0, 0, 0]
+    # preemptor 2: ERROR with used 0; a candidate had used gone to -1
+    assert list(m.res["count"][2]) == [0, 1, 0, 1, 0]
+    assert m.stats["quota_flags"] == 2
+
+
+def best_of(v):
+    return tuple(int(x) for x in v)
+
+
+def alone_with(m, pre):
+    return M.select_victims(m.cfg, m.table, m.assigned, m.pdb_allowed, pre)
+
+
+def test_tiles3_raises_the_pdb_flag_inside_the_second_tile():
+    m = S.case("tiles3")
+    assert len(m.pres) == S.TILES3_PRE == 65 and (len(m.pres) + 31) // 32 == 3
+    assert 257 <= m.table.n <= 300
+    k0 = S.TILES3_K0
+    assert 32 + 8 <= k0 < 64 - 8                         # well inside the second tile
+    a = m.assigned
+    assert S.TILES3_VICTIM in m.chosen[k0] and int(a["pdb_mask"][S.TILES3_VICTIM]) == 1
+    # no earlier victim spends the budget, so the flag rises with k0's pick and not before
+    assert not any(int(a["pdb_mask"][j]) for k in range(k0) for j in m.chosen[k])
+    assert m.stats["pdb_flag"] and m.stats["quota_flags"] == 0
+    assert m.stats["full_recomputes"] == len(m.pres) - 1 - k0
+    # up to k0 the answers are those without any PDB; after it a victim violates
+    plain = S.stream(m.cfg, m.table, _without_pdb(a), (), m.pres[:k0 + 1])[0]
+    assert plain.tobytes() == m.res[:k0 + 1].tobytes()
+    later = m.res["best"]["n_pdb_violations"][k0 + 1:]
+    assert not m.res["best"]["n_pdb_violations"][:k0 + 1].any() and (later > 0).any()
+    assert int(m.res["node"][64]) >= 0                   # the third tile's only preemptor has an answer to get wrong
+    assert (m.res["node"][32:k0] >= 0).any() and (m.res["node"][k0 + 1:64] >= 0).any()
+
+
+def _without_pdb(a):
+    b = a.copy()
+    b["pdb_mask"] = 0
+    return b
 
 
 @pytest.mark.parametrize("name", S.CASES)
