@@ -307,7 +307,12 @@ typedef struct koordhip_config {
 /* Columnar node snapshot, all arrays of length n, little-endian, caller-owned
  * and copied by koordhip_load_snapshot.  Units: CPU in milli-cores, memory /
  * ephemeral storage in bytes, batch-cpu as Quantity.Value().  Mutable columns
- * (requested / nz / npods / la_used*) are advanced on device by commits. */
+ * (requested / nz / npods / la_used*) are advanced on device by commits.
+ * Every resource quantity (alloc, requested, nz_*, la_alloc_*, la_used_*, the
+ * NUMA zone and reservation amounts, and koordhip_pod's req / nz_* / est_*)
+ * must be in [0, 2^45): load_snapshot, update_nodes and every call taking a
+ * pod record refuse any other value with KOORDHIP_EINVAL (the scores of a
+ * negative quantity leave [0, 100], the range the engine ranks in). */
 typedef struct koordhip_node_soa {
   /* NodeResourcesFit: NodeInfo.Allocatable (upstream framework/types.go) */
   const int64_t *alloc[KOORDHIP_NRES];

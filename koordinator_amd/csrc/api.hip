@@ -308,10 +308,14 @@ int upload(koordhip_ctx *c, T *dst, const T *src, size_t count) {
   return 0;
 }
 
-// Resource quantities live on device as exact f64 (eval.hpp): |v| < 2^45.
+// Resource quantities live on device as exact f64 (eval.hpp): 0 <= v < 2^45.
+// A negative one (no Allocatable, Requested, usage or pod request is) would
+// score above MaxNodeScore in the reference -- beyond the int32 planes for a
+// small capacity, and beyond the totals the ranking bins and keys are sized
+// for -- so it is refused like a too large one.
 constexpr int64_t kExact = 1ll << 45;
 
-bool exact_ok(int64_t v) { return v < kExact && v > -kExact; }
+bool exact_ok(int64_t v) { return v >= 0 && v < kExact; }
 
 // int64 quantity column -> f64 device column (NULL src -> zeros)
 int upload_q(koordhip_ctx *c, double *dst, const int64_t *src, size_t count, const char *what) {
@@ -323,7 +327,7 @@ int upload_q(koordhip_ctx *c, double *dst, const int64_t *src, size_t count, con
   std::vector<double> tmp(count);
   for (size_t i = 0; i < count; i++) {
     if (!exact_ok(src[i]))
-      return fail(KOORDHIP_EINVAL, std::string(what) + ": quantity magnitude >= 2^45 is outside the engine's exact range");
+      return fail(KOORDHIP_EINVAL, std::string(what) + ": quantity outside [0, 2^45), the engine's exact range");
     tmp[i] = (double)src[i];
   }
   HIP_TRY(hipMemcpyAsync(dst, tmp.data(), count * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -352,7 +356,7 @@ int to_dev_pods(const koordhip_pod *src, int32_t n, std::vector<kh::DevPod> &out
     std::memset(&o, 0, sizeof(o));
     const int64_t q[] = {p.req[0], p.req[1], p.req[2], p.req[3], p.req[4], p.nz_cpu_m, p.nz_mem, p.est_cpu, p.est_mem};
     for (int64_t v : q)
-      if (!exact_ok(v)) return fail(KOORDHIP_EINVAL, "pod quantity magnitude >= 2^45 is outside the engine's exact range");
+      if (!exact_ok(v)) return fail(KOORDHIP_EINVAL, "pod quantity outside [0, 2^45), the engine's exact range");
     for (int r = 0; r < KOORDHIP_NRES; r++) o.req[r] = (double)p.req[r];
     o.nz_cpu_m = (double)p.nz_cpu_m;
     o.nz_mem = (double)p.nz_mem;
@@ -578,7 +582,7 @@ int zone_rows(const int64_t *src, const int32_t *cls_of, const uint8_t *flags, c
     for (int q = 0; q < 2; q++)
       for (int k = 0; k < NM; k++) {
         const int64_t v = src[((size_t)i * 2 + q) * NM + k];
-        if (!exact_ok(v)) return fail(KOORDHIP_EINVAL, "numa zone: quantity magnitude >= 2^45 is outside the engine's exact range");
+        if (!exact_ok(v)) return fail(KOORDHIP_EINVAL, "numa zone: quantity outside [0, 2^45), the engine's exact range");
         if (k >= Z) {
           if (v != 0) return fail(KOORDHIP_EINVAL, "numa zone: values past the node's NUMA nodes must be 0");
           continue;
@@ -703,7 +707,7 @@ int check_resv_rows(const koordhip_node_soa *s, int32_t m) {
     for (int k = 0; k < 2; k++)
       if (s->resv_alloc[k][i] < 0 || s->resv_allocated[k][i] < 0 || s->resv_nz[k][i] < 0 || !exact_ok(s->resv_alloc[k][i]) ||
           !exact_ok(s->resv_allocated[k][i]) || !exact_ok(s->resv_nz[k][i]))
-        return fail(KOORDHIP_EINVAL, "reservation quantity out of range");
+        return fail(KOORDHIP_EINVAL, "reservation quantity out of [0, 2^45), the engine's exact range");
   }
   return 0;
 }
@@ -1740,7 +1744,7 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
       double *o = reinterpret_cast<double *>(img.data() + off[q]);
       for (int32_t j = 0; j < m; j++) {
         if (!exact_ok(src[j]))
-          return fail(KOORDHIP_EINVAL, std::string(k.what) + ": quantity magnitude >= 2^45 is outside the engine's exact range");
+          return fail(KOORDHIP_EINVAL, std::string(k.what) + ": quantity outside [0, 2^45), the engine's exact range");
         o[j] = (double)src[j];
       }
     } else {

@@ -3,9 +3,12 @@
 //
 // Exactness: the reference computes in int64.  On device every resource
 // quantity (node columns and pod records) is held as an f64 that IS that
-// integer: the host rejects magnitudes >= 2^45 (KH_EXACT_LIMIT), so sums,
-// differences, the x100 of leastRequestedScore and the division remainders
-// below are all integers < 2^53 and therefore exact in binary64.  The only
+// integer: the host admits quantities in [0, 2^45) only (KH_EXACT_LIMIT), so
+// sums, differences, the x100 of leastRequestedScore and the division
+// remainders below are all integers < 2^53 and therefore exact in binary64,
+// and every plugin score is in [0, 100]: a negative Requested would score
+// above 100 in the reference (past the int32 planes for a small capacity, and
+// past the totals the ranking kernels size their bins and keys for).  The only
 // divisions are quotients in [0, 101] (leastRequestedScore, weighted
 // averages): a reciprocal estimate, then one exact remainder fix-up in each
 // direction, equals Go's truncating int64 division bit for bit (lrs,
@@ -334,6 +337,9 @@ __device__ __forceinline__ void load_node(NV &v, const DevNodes &d, int32_t i, c
 // num / ws for the weighted averages (num <= 100 * sum of weights <= 50000,
 // ws <= 500): an f32 reciprocal estimate (relative error ~2^-23, so the
 // absolute error is < 0.01) truncated, then one exact int32 fix-up each way.
+// In this operand range only the upward one is ever taken (the estimate cannot
+// overshoot a boundary by 1 / ws >= 0.002); the downward one is kept as the
+// scheme's other half, for an estimate of any sign of error.
 __device__ __forceinline__ int32_t div_weights(int32_t num, int32_t ws) {
   int32_t q = (int32_t)((float)num * __builtin_amdgcn_rcpf((float)ws));
   const int32_t r = num - q * ws;

@@ -19,7 +19,15 @@ def _run(args, env=None):
 def test_gpus2_spawns_two_ranks():
     r = _run(["--gpus", "2", "--probe-ranks"])
     assert r.returncode == 0, r.stderr[-2000:]
-    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    # the ranks share the pipe: one's record may land before the other's newline,
+    # so read every JSON object of the output, not one per line
+    lines, dec, s = [], json.JSONDecoder(), r.stdout
+    at = s.find("{")
+    while at >= 0:
+        obj, end = dec.raw_decode(s, at)
+        lines.append(obj)
+        at = s.find("{", end)
+    assert len(lines) == 2, r.stdout
     assert sorted(x["rank"] for x in lines) == [0, 1]
     assert all(x["world"] == 2 for x in lines)
     assert sorted(x["local_rank"] for x in lines) == [0, 1]
