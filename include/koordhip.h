@@ -39,7 +39,8 @@
  *                              Reserve plugin.go:368-405 over nodeDevice (device_cache.go:44-482) and the
  *                              default allocator (allocator.go:91-122)
  *   static_score columns    <- (upstream) NodeAffinity / TaintToleration Score + NormalizeScore
- *   koordhip_diagnose / koordhip_fetch_diagnosis / koordhip_fetch_node_status
+ *   koordhip_diagnose / koordhip_fetch_diagnosis / koordhip_fetch_node_status /
+ *   koordhip_diagnose_ext / koordhip_node_status_ext
  *                           <- the Filter half of a failed cycle: framework.Diagnosis{NodeToStatusMap,
  *                              UnschedulablePlugins} of the FitError ((upstream) schedule_one.go findNodesThatFitPod),
  *                              read by frameworkext/eventhandlers/reservation_handler.go:92-94 and handed to every
@@ -696,6 +697,50 @@ int koordhip_fetch_diagnosis(koordhip_ctx *ctx, koordhip_diag *out /* [n_pods] *
  * PostFilter (preemption) for.  Same envelope and validity rule;
  * KOORDHIP_EINVAL for a pod that was placed. */
 int koordhip_fetch_node_status(koordhip_ctx *ctx, int32_t pod_index, uint8_t *status /* [n] */);
+
+/* ---- ... for the sequential cycle's profiles (additive to ABI 15: detect it
+ * by the symbols) ------------------------------------------------------------
+ * The two calls below answer for every profile and snapshot koordhip_eval_ext
+ * evaluates: DeviceShare, the extended scalars, PodTopologySpread,
+ * InterPodAffinity, the normalized NodeAffinity / TaintToleration Scores, and
+ * Reservation snapshots with more than KOORDHIP_RESV_SLOTS reservations on a
+ * node, topology-policy nodes or reservations holding devices.  Both evaluate
+ * against the CURRENT engine state and change none of it (a later
+ * koordhip_fetch_diagnosis still works).
+ *
+ * The record is the koordhip_diag above with four more slots filled: 5
+ * KOORDHIP_ST_DEVICE_FAIL, 6 KOORDHIP_ST_XFIT_FAIL, 7 KOORDHIP_ST_PTS_FAIL and 8
+ * KOORDHIP_ST_IPA_FAIL.  any[b] is the histogram of koordhip_eval_ext's status,
+ * with one difference: filterWithReservations' fitsNode covers the pod's
+ * extended scalars (reservation/plugin.go:445-494), so RESV is also set where
+ * only they fail the matched Aligned / Restricted reservations -- the
+ * reference's answer, which koordhip_eval_ext's RESV bit does not give yet.
+ * first[b] follows the framework's Filter order
+ *   STATIC -> FIT -> XFIT -> PTS -> IPA -> LA -> NUMA -> DEVICE -> RESV
+ * The first half is the (upstream) k8s v1.24 v1beta2 default plugin list --
+ * NodeUnschedulable / TaintToleration / NodeAffinity, NodeResourcesFit,
+ * PodTopologySpread, InterPodAffinity -- not vendored and therefore unpinned,
+ * like the rest of the upstream parity.  The second half is what
+ * config/manager/scheduler-config.yaml's filter.enabled list appends:
+ * LoadAwareScheduling, NodeNUMAResource, DeviceShare, Reservation.  XFIT is
+ * NodeResourcesFit on the extended scalars, the same plugin as FIT: the two are
+ * adjacent and a node failing both counts under FIT.  Restricted to the five
+ * older bits this is the order above, so a record without one of the new bits
+ * is identical to what the plain call gives; feasible + sum(first) = n holds.
+ *
+ * Validation is that of koordhip_eval_ext (the ext records against the
+ * profile and the snapshot's tables: KOORDHIP_EINVAL; no snapshot:
+ * KOORDHIP_ESTATE) and, as for the plain call, KOORDHIP_EINVAL for reserve /
+ * reservation-operating-mode pods.  ext may be NULL (no pod carries a record).
+ * Device traffic to the host is the records alone (136 B per pod): no
+ * per-(pod, node) plane exists on either side. */
+int koordhip_diagnose_ext(koordhip_ctx *ctx, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
+                          koordhip_diag *out /* [n_pods] */);
+/* One pod's NodeToStatusMap on the current state: status[n], the 16-bit
+ * KOORDHIP_ST_* bits koordhip_eval_ext reports for that pod (every plugin
+ * evaluated), without its score planes and per-call buffers. */
+int koordhip_node_status_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const koordhip_pod_ext *ext,
+                             uint16_t *status /* [n] */);
 
 /* ---- preemption dry run (additive to ABI 15: detect it by the symbols) -----
  * The PostFilter of elasticquota/plugin.go:310-329: SelectVictimsOnNode

@@ -233,6 +233,11 @@ DIAG_DTYPE = np.dtype([("feasible", "<i4"), ("reserved", "<i4"), ("any", "<i4", 
 assert DIAG_DTYPE.itemsize == 136
 # the framework's Filter order behind `first` (include/koordhip.h)
 FILTER_ORDER = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_LA_FAIL, ST_NUMA_FAIL, ST_RESV_FAIL)
+# ... with the sequential cycle's plugins (koordhip_diagnose_ext): the (upstream) default list, then the
+# koordinator plugins as scheduler-config.yaml's filter.enabled appends them; XFIT is NodeResourcesFit too
+FILTER_ORDER_EXT = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_XFIT_FAIL, ST_PTS_FAIL, ST_IPA_FAIL, ST_LA_FAIL, ST_NUMA_FAIL,
+                    ST_DEVICE_FAIL, ST_RESV_FAIL)
+DIAG_EXT_POD_TILE = 32  # pods per workgroup of koordhip_diagnose_ext's kernel (diag_ext.hip DIAGX_PT)
 # the preemption dry run (koordhip_preempt*): numpy twins of koordhip_assigned (160 bytes),
 # koordhip_preemptor (208), koordhip_preempt_node (32) and koordhip_preempt_result (56)
 PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
@@ -301,6 +306,8 @@ class KoordhipError(RuntimeError):
 
 
 _lib = None
+# additive to ABI 15 (no version bump): a build without them still loads
+ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext")
 
 
 def load_library(path: str = LIB_PATH):
@@ -348,6 +355,8 @@ def load_library(path: str = LIB_PATH):
         "koordhip_diagnose": (C.c_int, [vp, vp, C.c_int32, vp]),
         "koordhip_fetch_diagnosis": (C.c_int, [vp, vp, C.c_int32]),
         "koordhip_fetch_node_status": (C.c_int, [vp, C.c_int32, _u8p]),
+        "koordhip_diagnose_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp]),
+        "koordhip_node_status_ext": (C.c_int, [vp, vp, vp, C.POINTER(C.c_uint16)]),
         "koordhip_preempt_load_pods": (C.c_int, [vp, vp, C.c_int32, _i32p, C.c_int32]),
         "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
@@ -368,6 +377,8 @@ def load_library(path: str = LIB_PATH):
         "koordhip_comm_init_local": (C.c_int, [C.POINTER(vp), C.c_int32]),
     }
     for name, (res, args) in sig.items():
+        if name in ADDITIVE_SYMBOLS and not hasattr(lib, name):
+            continue    # an older ABI 15 build (KOORDHIP_LIB): the call is detected by its symbol
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
@@ -385,6 +396,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_synchronize", "koordhip_checkpoint", "koordhip_restore", "koordhip_commit", "koordhip_uncommit",
     "koordhip_commit_ext", "koordhip_uncommit_ext",
     "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
+    "koordhip_diagnose_ext", "koordhip_node_status_ext",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_preempt_stream",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",

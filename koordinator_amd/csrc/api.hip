@@ -21,6 +21,7 @@
 #include "../../include/koordhip.h"
 #include "cls.h"
 #include "diag.h"
+#include "diag_ext.h"
 #include "preempt.h"
 #include "kernels.h"
 #include "seq.h"
@@ -264,6 +265,9 @@ struct koordhip_ctx {
   void *d_diag_rec = nullptr;      // records / one pod's status bytes
   void *d_diag_pods = nullptr;     // koordhip_diagnose's pods
   size_t diag_ws_cap = 0, diag_rec_cap = 0, diag_pods_cap = 0;
+  void *d_diagx_podx = nullptr;    // koordhip_diagnose_ext's ext records (diag_ext.hip)
+  void *d_diagx_ws = nullptr;      // ... and its pre-passes' results (kh::diag_ext_ws_bytes)
+  size_t diagx_podx_cap = 0, diagx_ws_cap = 0;
   // preemption dry run (preempt.hip)
   bool pre_loaded = false;         // koordhip_preempt_load_pods ran on this snapshot
   int32_t pre_m = 0;               // its assigned pods
@@ -1299,7 +1303,7 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_podx, (void *)c->d_devout, (void *)c->d_seqg, c->d_seqdesc, (void *)c->d_pod_cls,
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
                   (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
-                  c->d_diag_rec, c->d_diag_pods, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out,
+                  c->d_diag_rec, c->d_diag_pods, c->d_diagx_podx, c->d_diagx_ws, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out,
                   c->d_pre_st})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
@@ -3749,6 +3753,75 @@ int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *stat
   HIP_TRY(hipMemcpyAsync(status, c->d_diag_rec, (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// ---- ... for every profile koordhip_eval_ext evaluates (diag_ext.hip) -------
+
+// koordhip_diagnose_ext (out: n_pods records) and koordhip_node_status_ext
+// (status: one pod's [n] words): koordhip_eval_ext's validation and
+// koordhip_diagnose's, then the pods into the context's workspaces and one
+// pass of k_diag_ext.  Answers against the current state; touches neither it
+// nor diag_valid.
+static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
+                             koordhip_diag *out, uint16_t *status) {
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
+  if (n_pods == 0) return 0;
+  bool any = false;
+  if (ext) {
+    if (int e = check_pod_ext(ext, n_pods, &any)) return e;
+    if (int e = check_pod_pts(c, ext, n_pods)) return e;
+  }
+  if (any && !c->seq_profile)
+    return fail(KOORDHIP_EINVAL, "device / extended-scalar pod requests need DeviceShare in the profile");
+  bool reserve = false;
+  if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
+  if (reserve)
+    return fail(KOORDHIP_EINVAL, "koordhip_diagnose_ext: reserve / reservation-operating-mode pods are not covered");
+  std::vector<kh::DevPod> hp;
+  if (int e = to_dev_pods(pods, n_pods, hp, ext, devshare_resv_on(c))) return e;
+  // the hostname minima are reduced only when a pod has a hard constraint on a hostname key (PtsPod::hhost)
+  bool hhost = false;
+  if (ext && c->pts.filt && c->pts.keys > 0)
+    for (int32_t j = 0; j < n_pods && !hhost; j++)
+      for (int q = 0; q < ext[j].pts_n; q++)
+        hhost = hhost || ((ext[j].pts_fl[q] & KOORDHIP_PTS_HARD) && ((c->pts.host >> c->pts.cons_key[ext[j].pts_c[q]]) & 1u));
+  HIP_TRY(hipSetDevice(c->device));
+  const int32_t n = c->n;
+  if (n == 0) {
+    if (out) std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_diag));
+    return 0;
+  }
+  const size_t pb = (size_t)n_pods * sizeof(kh::DevPod), xb = (size_t)n_pods * sizeof(kh::DevPodX);
+  const size_t rb = status ? (size_t)n * sizeof(uint16_t) : (size_t)n_pods * sizeof(koordhip_diag);
+  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, pb)) return e;
+  if (ext)
+    if (int e = ensure(c, &c->d_diagx_podx, &c->diagx_podx_cap, xb)) return e;
+  if (int e = ensure(c, &c->d_diagx_ws, &c->diagx_ws_cap, kh::diag_ext_ws_bytes(n_pods))) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), pb, hipMemcpyHostToDevice, c->stream));
+  if (ext) HIP_TRY(hipMemcpyAsync(c->d_diagx_podx, ext, xb, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  const int32_t rs = (c->dc.resv && (c->cfg.score_plugins & KOORDHIP_PLUGIN_RESERVATION)) ? 1 : 0;
+  HIP_TRY(kh::launch_diag_ext(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods),
+                              ext ? static_cast<const kh::DevPodX *>(c->d_diagx_podx) : nullptr, n_pods, rs, c->pts, c->ipa,
+                              c->d_diagx_ws, hhost, status ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
+                              status ? static_cast<uint16_t *>(c->d_diag_rec) : nullptr, c->stream));
+  HIP_TRY(hipMemcpyAsync(status ? static_cast<void *>(status) : static_cast<void *>(out), c->d_diag_rec, rb,
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int koordhip_diagnose_ext(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
+                          koordhip_diag *out) {
+  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diagnose_ext_impl(c, pods, ext, n_pods, out, nullptr);
+}
+
+int koordhip_node_status_ext(koordhip_ctx *c, const koordhip_pod *pod, const koordhip_pod_ext *ext, uint16_t *status) {
+  if (!c || !pod || !status) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diagnose_ext_impl(c, pod, ext, 1, nullptr, status);
 }
 
 // ---- preemption dry run (preempt.hip) --------------------------------------

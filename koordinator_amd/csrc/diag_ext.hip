@@ -1,0 +1,286 @@
+// diag_ext.hip -- why a pod is unschedulable under the profiles and snapshots
+// of the sequential cycle (DeviceShare, the extended scalars, PodTopologySpread,
+// InterPodAffinity, the 8-slot / device-holding Reservation rows): koordhip_diag
+// records over the nine status bits, reduced on device like diag.hip's -- no
+// [pods][n] plane exists anywhere.
+//
+//   k_diag_pts_sums   once per call: the pod-independent counters
+//                     PodTopologySpread's Filter reads (PtsSums: what pts_init
+//                     rebuilds per workgroup by sweeping every node), summed
+//                     over the grid; resets the pods' hostname minima.
+//   k_diag_hmin       once per call, when a pod has a hard hostname constraint:
+//                     hmin[p] = the minimum of pts_host_match over the eligible
+//                     nodes (k_pts_eval's, as a grid reduction).
+//   (k_ipa_sums)      InterPodAffinity's domain sums, seq.hip's kernel.
+//   k_diag_ext<SM>    256-node tiles x pod tiles, SM as in seq_mode.  A thread
+//                     owns one node: it loads the row filter_status reads once
+//                     and loops over the tile's pods, whose DevPod / DevPodX
+//                     records are staged in LDS.  Per pod the workgroup derives
+//                     the hard keys' pair counters and minima from the sums
+//                     (pts_prep: 256 threads and a barrier); the status is
+//                     filter_status on the restored row | seq_eval's bits |
+//                     pts_filter | ipa_filter, each the one definition the
+//                     cycle and koordhip_eval_ext use.  Counting is diag.hip's:
+//                     one ballot + popcount per wave and counter into an LDS
+//                     table of whole records, flushed with atomics on
+//                     consecutive words.  With a status pointer (one pod) the
+//                     node's 16-bit status is stored instead.
+//
+// None of this is cached across calls: every Reserve advances pts_cnt / ipa_cnt.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "diag.h"
+#include "diag_ext.h"
+#include "seq.h"
+#include "seq_eval.hpp"
+
+namespace kh {
+
+constexpr int DIAGX_THREADS = 256;
+constexpr int DIAGX_POD_WORDS = (int)(sizeof(DevPod) / sizeof(uint64_t));
+constexpr int DIAGX_PODX_WORDS = (int)(sizeof(DevPodX) / sizeof(uint64_t));
+constexpr int DIAGX_ANY = (int)(offsetof(koordhip_diag, any) / sizeof(int32_t));
+constexpr int DIAGX_FIRST = (int)(offsetof(koordhip_diag, first) / sizeof(int32_t));
+constexpr int DIAGX_NBITS = 9;  // status bits 0..8: FIT, LA, NUMA, RESV, STATIC, DEVICE, XFIT, PTS, IPA
+static_assert(sizeof(DevPod) % sizeof(uint64_t) == 0 && sizeof(DevPodX) % sizeof(uint64_t) == 0,
+              "pod records are staged as 8-B words");
+static_assert(offsetof(DevPodX, req) == 0 && DT >= 1 && DR == 3, "the empty record: req[0][0..2] = -1 are words 0..2");
+static_assert(KOORDHIP_ST_IPA_FAIL == 1u << (DIAGX_NBITS - 1), "the counted status bits are bits 0..8");
+static_assert(PK * 64 <= DIAGX_THREADS, "pts_prep: one wave per topology key");
+
+// The first failing plugin in the framework's Filter order (koordhip.h):
+// STATIC -> FIT -> XFIT -> PTS -> IPA -> LA -> NUMA -> DEVICE -> RESV.
+// Restricted to diag.hip's five bits it is that file's first_fail.
+__device__ __forceinline__ uint32_t first_fail_ext(uint32_t st) {
+  constexpr uint32_t order[DIAGX_NBITS] = {KOORDHIP_ST_STATIC_FAIL, KOORDHIP_ST_FIT_FAIL,    KOORDHIP_ST_XFIT_FAIL,
+                                           KOORDHIP_ST_PTS_FAIL,    KOORDHIP_ST_IPA_FAIL,    KOORDHIP_ST_LA_FAIL,
+                                           KOORDHIP_ST_NUMA_FAIL,   KOORDHIP_ST_DEVICE_FAIL, KOORDHIP_ST_RESV_FAIL};
+  uint32_t f = 0u;
+#pragma unroll
+  for (int k = DIAGX_NBITS - 1; k >= 0; k--) f = (st & order[k]) ? order[k] : f;
+  return f;
+}
+
+// One wave's 64 nodes into a pod's LDS record (diag.hip's diag_count over the
+// nine bits).  Called by every lane of the wave; lanes not `live` count nowhere.
+__device__ __forceinline__ void diag_count_ext(uint32_t st, bool live, int32_t *rec) {
+  const uint32_t f = first_fail_ext(st);
+  const bool l0 = __lane_id() == 0;
+  const uint64_t ok = __ballot(live && st == 0u);
+  if (l0 && ok) atomicAdd(&rec[0], (int32_t)__popcll(ok));
+#pragma unroll
+  for (int b = 0; b < DIAGX_NBITS; b++) {
+    const uint64_t ma = __ballot(live && ((st >> b) & 1u) != 0u);
+    const uint64_t mf = __ballot(live && f == (1u << b));
+    if (l0 && ma) atomicAdd(&rec[DIAGX_ANY + b], (int32_t)__popcll(ma));
+    if (l0 && mf) atomicAdd(&rec[DIAGX_FIRST + b], (int32_t)__popcll(mf));
+  }
+}
+
+// ---------------------------------------------------------------------------
+// the pre-passes
+
+// sums zeroed by the caller; one workgroup-local table per block, then one
+// global atomic per nonzero cell (the arithmetic of pts_init's fsum / fpres)
+__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_pts_sums(PtsArgs pa, int32_t n, PtsSums *__restrict__ sums,
+                                                                 int32_t *__restrict__ hmin, int32_t n_pods) {
+  __shared__ PtsSums s;
+  constexpr int NF = PC * PD, NP = PS * PK * 2;
+  int32_t *sf = &s.fsum[0][0];
+  uint32_t *sp = &s.fpres[0][0][0];
+  const int t = threadIdx.x;
+  const int32_t gid = (int32_t)(blockIdx.x * blockDim.x) + t, gsz = (int32_t)(gridDim.x * blockDim.x);
+  for (int32_t p = gid; p < n_pods; p += gsz) hmin[p] = INT32_MAX;
+  for (int x = t; x < NF; x += DIAGX_THREADS) sf[x] = 0;
+  for (int x = t; x < NP; x += DIAGX_THREADS) sp[x] = 0u;
+  __syncthreads();
+  for (int32_t i = gid; i < n; i += gsz) {
+    const uint32_t el = pa.elig[i];
+    for (int k = 0; k < pa.keys; k++) {
+      if ((pa.host >> k) & 1u) continue;
+      const int32_t d = pa.dom[(size_t)k * n + i];
+      if (d < 0 || d >= PD) continue;
+      for (int c = 0; c < pa.classes; c++)
+        if ((el >> (2 * c)) & 1u) atomicOr(&s.fpres[c][k][d >> 5], 1u << (d & 31));
+    }
+    for (int c = 0; c < pa.cons; c++) {
+      const int k = pa.cons_key[c];
+      if ((pa.host >> k) & 1u) continue;
+      const int32_t d = pa.dom[(size_t)k * n + i];
+      const int32_t v = pa.cnt[(size_t)c * n + i];
+      if (d < 0 || d >= PD || v == 0) continue;
+      atomicAdd(&s.fsum[c][d], v);
+    }
+  }
+  __syncthreads();
+  for (int x = t; x < NF; x += DIAGX_THREADS)
+    if (sf[x]) atomicAdd(&sums->fsum[0][0] + x, sf[x]);
+  for (int x = t; x < NP; x += DIAGX_THREADS)
+    if (sp[x]) atomicOr(&sums->fpres[0][0][0] + x, sp[x]);
+}
+
+// workgroup (p, y): pod p over the nodes y 256, (y + gridDim.y) 256, ...
+__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_hmin(PtsArgs pa, int32_t n, const DevPodX *__restrict__ podx,
+                                                             int32_t *__restrict__ hmin) {
+  const int32_t p = (int32_t)blockIdx.x;
+  const PtsPod q = pts_pod(pa, podx[p]);
+  if (!q.hhost) return;
+  int32_t m = INT32_MAX;
+  for (int32_t i = (int32_t)blockIdx.y * DIAGX_THREADS + (int32_t)threadIdx.x; i < n;
+       i += (int32_t)gridDim.y * DIAGX_THREADS)
+    for (int k = 0; k < PK; k++)
+      if (((q.hkeys & pa.host) >> k) & 1u) {
+        const int32_t v = pts_host_match(pa, q, k, n, i);
+        if (v >= 0) m = min(m, v);
+      }
+  m = pts_wave_min(m);
+  if (__lane_id() == 0 && m != INT32_MAX) atomicMin(&hmin[p], m);
+}
+
+// ---------------------------------------------------------------------------
+// k_diag_ext
+
+template <int SM>
+__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_ext(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
+                                                            const DevPodX *__restrict__ podx, int32_t n_pods,
+                                                            int32_t rs, PtsArgs pa, IpaArgs ia,
+                                                            const PtsSums *__restrict__ psum,
+                                                            const int32_t *__restrict__ hmin, int32_t *__restrict__ out,
+                                                            uint16_t *__restrict__ status) {
+  constexpr int S = SM >= 2 ? kSeqSlots<SM> : 1;  // the reservation slots of filter_status' side row
+  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAGX_PT * DIAGX_POD_WORDS];
+  __shared__ __attribute__((aligned(16))) uint64_t sxw[DIAGX_PT * DIAGX_PODX_WORDS];
+  __shared__ int32_t tab[DIAGX_PT * kDiagWords];
+  __shared__ PtsLds L;   // fsum / fpres from the call's sums; fmatch / fmin per pod (ssum: Score only, never read)
+  __shared__ IpaLds IL;
+  const int t = threadIdx.x;
+  const int32_t p0 = (int32_t)blockIdx.y * DIAGX_PT;
+  const int32_t np = min(DIAGX_PT, n_pods - p0);
+  const uint64_t *src = reinterpret_cast<const uint64_t *>(pods + p0);
+  for (int32_t w = t; w < np * DIAGX_POD_WORDS; w += DIAGX_THREADS) spw[w] = src[w];
+  if (podx) {
+    const uint64_t *sx = reinterpret_cast<const uint64_t *>(podx + p0);
+    for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAGX_THREADS) sxw[w] = sx[w];
+  } else {  // the record of a pod without koordhip_pod_ext (no device request: gpu -1 = key absent)
+    for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAGX_THREADS) sxw[w] = (w % DIAGX_PODX_WORDS) < DR ? ~0ull : 0ull;
+  }
+  for (int32_t w = t; w < np * kDiagWords; w += DIAGX_THREADS) tab[w] = 0;
+  const bool pts_on = pa.filt && pa.keys > 0;
+  const bool ipa_on = ia.filt && ia.ents > 0;
+  if (pts_on) {
+    for (int x = t; x < PC * PD; x += DIAGX_THREADS) (&L.fsum[0][0])[x] = (&psum->fsum[0][0])[x];
+    for (int x = t; x < PS * PK * 2; x += DIAGX_THREADS) (&L.fpres[0][0][0])[x] = (&psum->fpres[0][0][0])[x];
+  }
+  if (ipa_on) ipa_load(ia, IL, t, DIAGX_THREADS);
+  __syncthreads();
+  const DevPod *sp = reinterpret_cast<const DevPod *>(spw);
+  const DevPodX *sx = reinterpret_cast<const DevPodX *>(sxw);
+  const int32_t i = (int32_t)blockIdx.x * DIAGX_THREADS + t;
+  const bool live = i < d.n;
+  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
+  NV v{};
+  const Need all = need_all(c);
+  load_node(v, d, il, all, c);
+  NumaRowRS<S> nr{};
+  load_numa<true>(nr, d, il, all);
+  if constexpr (S > 1) {
+    if (c.resv) {
+      load_resv(nr, d.rv, il);
+      // a topology-policy node's zone row shares the reserved CPUs' bytes (the Filter reads the zones only)
+      if (c.zones && topo_policy(nr.nflags) != 0) load_zones(nr, d, il);
+    }
+  }
+  for (int32_t q = 0; q < np; q++) {  // wave-uniform: the ballots and the barriers are valid
+    const DevPod &pod = sp[q];
+    const DevPodX &x = sx[q];
+    NV w = v;
+    int nmatch = 0;
+    uint32_t mm = 0;
+    ResvXS rx = no_rx();
+    if constexpr (S > 1) {
+      if (c.resv) {
+        // the cycle's restore: every plugin sees the restored node, with the extended
+        // scalars of a reservation holding devices (what eval_total_resv restores and filters with)
+        rx = seq_resv_x(d, pod, x, nr, il);
+        nmatch = resv_restore(w, nr, pod, mm, rx);
+        // filterWithReservations' fitsNode covers the pod's extended scalars on every node.  Where no
+        // reservation holds devices they are the node's own: a node failing xfit_filter fails the fit of
+        // every matched Aligned / Restricted reservation -- a ResvXS naming no slot (h = S) without RX_FIT_O.
+        if (rx.h < 0 && !xfit_filter(d.dv, x, il, d.n)) rx = ResvXS{S, RX_FIT_H | RX_LE | RX_XFIT, 0, 0};
+      }
+    }
+    uint32_t st = filter_status(c, pod, w, nr, d.nu.cls, nmatch, mm, rx);
+    int32_t raw[KOORDHIP_NEXT_PLUGINS];
+    uint8_t sq = 0;
+    (void)seq_eval<SM>(c, d, pod, x, il, rs != 0, raw, &sq);  // XFIT, DEVICE, RESV of a reserve pod
+    st |= sq;
+    // PodTopologySpread's Filter half only: pts_prep then never reads the Score's ssum
+    PtsPod pq = pts_pod(pa, x);
+    pq.soft = pq.skeys = 0u;
+    pq.ns = 0;
+    const bool spread = pts_on && pq.nh > 0;
+    if (spread) {
+      pts_prep(pa, pq, L, t);  // (ends with a barrier)
+      if (!pts_filter(pa, pq, L, pq.hhost ? hmin[p0 + q] : INT32_MAX, d.n, il)) st |= KOORDHIP_ST_PTS_FAIL;
+    }
+    if (ipa_on && (x.ipa_aff | x.ipa_anti) != 0u && !ipa_filter(ia, IL, x, d.n, il)) st |= KOORDHIP_ST_IPA_FAIL;
+    if (status) {
+      if (live) status[i] = (uint16_t)st;
+    } else {
+      diag_count_ext(st, live, tab + q * kDiagWords);
+    }
+    if (spread) __syncthreads();  // the next pod's pts_prep overwrites fmatch / fmin
+  }
+  __syncthreads();
+  if (!status)
+    for (int32_t w = t; w < np * kDiagWords; w += DIAGX_THREADS) {
+      const int32_t x = tab[w];
+      if (x) atomicAdd(&out[(size_t)p0 * kDiagWords + w], x);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host-side launch wrapper
+
+hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
+                           int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
+                           uint16_t *status, hipStream_t s) {
+  if (n_pods <= 0 || d.n <= 0) return hipSuccess;
+  if ((status && n_pods != 1) || (!status && !out) || !ws) return hipErrorInvalidValue;
+  const dim3 grid((d.n + DIAGX_THREADS - 1) / DIAGX_THREADS, (n_pods + DIAGX_PT - 1) / DIAGX_PT);
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  PtsSums *psum = static_cast<PtsSums *>(ws);
+  int32_t *hmin = reinterpret_cast<int32_t *>(psum + 1);
+  const int32_t nblk = std::min<int32_t>(1024, (d.n + DIAGX_THREADS - 1) / DIAGX_THREADS);
+  if (ipa.filt)
+    if (hipError_t e = launch_ipa_sums(ipa, d.n, s)) return e;
+  if (pts.filt && pts.keys > 0) {
+    if (hipError_t e = hipMemsetAsync(psum, 0, sizeof(PtsSums), s)) return e;
+    hipLaunchKernelGGL(k_diag_pts_sums, dim3(nblk), dim3(DIAGX_THREADS), 0, s, pts, d.n, psum, hmin, n_pods);
+    if (hhost && podx)
+      hipLaunchKernelGGL(k_diag_hmin, dim3(n_pods, std::min<int32_t>(64, nblk)), dim3(DIAGX_THREADS), 0, s, pts, d.n, podx,
+                         hmin);
+  }
+  switch (seq_mode(c)) {
+    case 3:
+      hipLaunchKernelGGL(k_diag_ext<3>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+                         out, status);
+      break;
+    case 2:
+      hipLaunchKernelGGL(k_diag_ext<2>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+                         out, status);
+      break;
+    case 1:
+      hipLaunchKernelGGL(k_diag_ext<1>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+                         out, status);
+      break;
+    default:
+      hipLaunchKernelGGL(k_diag_ext<0>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+                         out, status);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace kh

@@ -874,11 +874,13 @@ __device__ __attribute__((noinline)) bool numa_reserve(const DevNumaClass *class
 // enabled Filter plugin that fails.  v / r: the node's values after the
 // cycle's Reservation restore (nmatch / mm: its matched reservations; 0
 // without reservation columns).  The one definition koordhip_eval's parity
-// kernel and the diagnosis kernels (diag.hip) share.
+// kernel and the diagnosis kernels (diag.hip, diag_ext.hip) share.  rx: the
+// extended scalars of the node's reservation holding devices (resv.hpp), for
+// the caller that restored with them (diag_ext.hip); none otherwise.
 template <int S>
 __device__ __forceinline__ uint32_t filter_status(const DevCfg &c, const DevPod &pod, const NV &v,
                                                   const NumaRowRS<S> &r, const DevNumaClass *classes, int nmatch,
-                                                  uint32_t mm) {
+                                                  uint32_t mm, ResvXS rx = no_rx()) {
   uint32_t b = 0;
   if ((c.filt & KOORDHIP_PLUGIN_NODE_STATIC) && !((v.sa >> pod.sclass) & 1u)) b |= KOORDHIP_ST_STATIC_FAIL;
   if ((c.filt & KOORDHIP_PLUGIN_FIT) && !fit_filter(pod, v)) b |= KOORDHIP_ST_FIT_FAIL;
@@ -886,7 +888,7 @@ __device__ __forceinline__ uint32_t filter_status(const DevCfg &c, const DevPod 
   if ((c.filt & KOORDHIP_PLUGIN_NUMA) && (!numa_filter<true>(pod, r, classes) || (c.amp && !amp_filter_ok(pod, v, r))))
     b |= KOORDHIP_ST_NUMA_FAIL;
   if ((c.filt & KOORDHIP_PLUGIN_RESERVATION) &&
-      (nmatch > 0 ? !resv_filter(pod, v, r, mm, nmatch) : (pod.flags & KOORDHIP_POD_RESV_AFFINITY) != 0))
+      (nmatch > 0 ? !resv_filter(pod, v, r, mm, nmatch, rx) : (pod.flags & KOORDHIP_POD_RESV_AFFINITY) != 0))
     b |= KOORDHIP_ST_RESV_FAIL;
   return b;
 }

@@ -43,6 +43,10 @@ constexpr size_t seq_desc_bytes() { return seq_desc_cfg_bytes() + sizeof(DevNode
 hipError_t launch_seq_eval(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
                            int32_t rs, uint8_t *status, uint8_t *ipa_status, int32_t *scores, int32_t *work, int32_t k,
                            uint64_t *topk, const PtsArgs &pts, const IpaArgs &ipa, hipStream_t s);
+// k_ipa_sums on its own (diag_ext.hip's pre-pass): ipa.sums = the count
+// entries' domain sums over the n nodes, as launch_seq / launch_seq_eval make
+// them for themselves.  No entries: nothing.
+hipError_t launch_ipa_sums(const IpaArgs &ipa, int32_t n, hipStream_t s);
 // Reserve (sign > 0) / Unreserve (sign < 0) of one pod with its ext record on
 // `node` (koordhip_commit_ext / koordhip_uncommit_ext); one device thread.  cpus
 // [NW], dev [DT]: Reserve's outputs, Unreserve's inputs; rc: 0 / KOORDHIP_ERESERVE

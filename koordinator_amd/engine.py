@@ -257,6 +257,31 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_diagnose(self._ctx, pods.ctypes.data, len(pods), out.ctypes.data))
         return out
 
+    def diagnose_ext(self, pods: np.ndarray, ext: Optional[np.ndarray] = None) -> np.ndarray:
+        """diagnose() for every profile and snapshot, the sequential cycle's
+        included (DeviceShare, the extended scalars, PodTopologySpread,
+        InterPodAffinity): records whose `first` follows abi.FILTER_ORDER_EXT."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        x = None if ext is None else np.ascontiguousarray(ext, dtype=abi.POD_EXT_DTYPE)
+        out = np.zeros(len(pods), abi.DIAG_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_diagnose_ext(self._ctx, pods.ctypes.data,
+                                                           x.ctypes.data if x is not None else None, len(pods),
+                                                           out.ctypes.data))
+        return out
+
+    def node_status_ext(self, pod, ext=None) -> np.ndarray:
+        """[n] 16-bit abi.ST_* status words of one pod against the current
+        state: eval_ext's status row without its planes."""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        x = None if ext is None else np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        if len(pod) != 1 or (x is not None and len(x) != 1):
+            raise ValueError("node_status_ext takes one pod")
+        out = np.zeros(self.n, np.uint16)
+        abi.check(self.lib, self.lib.koordhip_node_status_ext(self._ctx, pod.ctypes.data,
+                                                              x.ctypes.data if x is not None else None,
+                                                              abi.ptr(out, C.c_uint16)))
+        return out
+
     def fetch_diagnosis(self, n: int) -> np.ndarray:
         """The records of the last place call's unplaced pods (out_node < 0) at
         the state each was decided on; all-zero records for placed pods."""

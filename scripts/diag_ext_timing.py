@@ -1,0 +1,91 @@
+"""Host wall time of a FitError's Filter half under the DeviceShare profile: the
+cluster of `bench.py --workload deviceshare` (50k nodes, 30 % with GPUs) and
+1,000 pods with 20 % device pods, three routes alternating in one process:
+
+  (a) diagnose_ext of the 1,000 pods                       (k_diag_ext: 136 B per pod to the host)
+  (b) eval_ext(status) of the same pods, the call alone and with the numpy
+      histogram that turns its planes into records         (the only route before diagnose_ext)
+  (c) node_status_ext of one pod
+
+Each figure is the median of --reps timed calls after --warmup untimed rounds;
+every call synchronises.  Prints one JSON line.  Run it twice to see the spread.
+
+    python scripts/diag_ext_timing.py [--nodes 50000] [--pods 1000] [--reps 7] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def histogram(status: np.ndarray, order, dtype) -> np.ndarray:
+    """koordhip_diag records of [p][n] status words (the host's share of route b)."""
+    st = status.astype(np.uint32)
+    rec = np.zeros(len(st), dtype)
+    rec["feasible"] = (st == 0).sum(axis=1)
+    left = np.ones(st.shape, bool)
+    for bit in order:
+        b = bit.bit_length() - 1
+        has = (st & bit) != 0
+        rec["any"][:, b] = has.sum(axis=1)
+        rec["first"][:, b] = (has & left).sum(axis=1)
+        left &= ~has
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nodes", type=int, default=50000)
+    ap.add_argument("--pods", type=int, default=1000)
+    ap.add_argument("--dev-frac", type=float, default=0.2)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    args = ap.parse_args()
+    import torch  # noqa: F401  (device discovery only)
+    from koordinator_amd import abi, synth
+    from koordinator_amd.config import shipped_profile, with_deviceshare
+    from koordinator_amd.engine import PlacementEngine
+
+    prof = with_deviceshare(shipped_profile())
+    c = synth.CONFIGS[4]
+    table = synth.make_cluster(synth.ClusterSpec(args.nodes), prof)
+    synth.add_devices(table, synth.DevSpec())
+    pods = synth.make_pods(synth.StreamSpec(args.pods, be_frac=c["be_frac"]), prof)
+    ext = synth.make_device_ext(args.pods, synth.DevStreamSpec(frac=args.dev_frac))
+    t = {"diagnose_ext": [], "eval_ext_status": [], "eval_ext_status_histogram": [], "node_status_ext": []}
+    with PlacementEngine(prof, device=0) as eng:
+        eng.load_snapshot(table)
+        rec = None
+        for r in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            rec = eng.diagnose_ext(pods, ext)
+            t1 = time.perf_counter()
+            st = eng.eval_ext(pods, ext, status=True, scores=False)["status"]
+            t2 = time.perf_counter()
+            ref = histogram(st, abi.FILTER_ORDER_EXT, abi.DIAG_DTYPE)
+            t3 = time.perf_counter()
+            row = eng.node_status_ext(pods[0], ext[0])
+            t4 = time.perf_counter()
+            if r >= args.warmup:
+                t["diagnose_ext"].append(t1 - t0)
+                t["eval_ext_status"].append(t2 - t1)
+                t["eval_ext_status_histogram"].append(t3 - t1)
+                t["node_status_ext"].append(t4 - t3)
+        same = rec.tobytes() == ref.tobytes() and np.array_equal(row, st[0])
+    out = {"nodes": args.nodes, "pods": args.pods, "dev_frac": args.dev_frac, "reps": args.reps,
+           "routes_agree": bool(same)}
+    for k, v in t.items():
+        out[k + "_ms"] = round(statistics.median(v) * 1e3, 3)
+        out[k + "_ms_min_max"] = [round(min(v) * 1e3, 3), round(max(v) * 1e3, 3)]
+    print(json.dumps(out))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())
