@@ -25,6 +25,7 @@
 #include "preempt.h"
 #include "kernels.h"
 #include "seq.h"
+#include "snapshot_cols.hpp"
 
 namespace {
 
@@ -109,7 +110,7 @@ struct koordhip_ctx {
   int32_t partial_r = 2;    // nodes per lane of k_scan (tuning knob KOORDHIP_TOPK_R)
   int32_t scan_ppw = 0;     // pods per node-major scan wave: 0 = pod-major k_scan, -1 auto (KOORDHIP_SCAN_PPW)
 
-  std::vector<void *> cols;  // every device column allocation
+  std::vector<kh::Column> cols;  // the snapshot's column table (snapshot_cols.hpp): every device column
   kh::DevNodes d{};
   kh::PrepIn prep{};
 
@@ -167,8 +168,6 @@ struct koordhip_ctx {
   std::vector<uint8_t> upd_host;   // its host image
   uint64_t *d_dbg = nullptr;  // KOORDHIP_STAMPS diagnostic counters (resolve segments)
 
-  // checkpoint of the mutable columns
-  std::vector<void *> ckpt;
   std::vector<kh::DevNumaClass> host_classes;  // the loaded topology classes (host copy)
 
   // sharding
@@ -283,17 +282,13 @@ struct koordhip_ctx {
 
 namespace {
 
-template <typename T>
-int dev_alloc(koordhip_ctx *c, T **p, size_t count) {
-  void *q = nullptr;
-  HIP_TRY(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-  c->cols.push_back(q);
-  *p = static_cast<T *>(q);
-  return 0;
-}
+using kh::exact_ok;
 
 void free_cols(koordhip_ctx *c) {
-  for (void *p : c->cols) (void)hipFree(p);
+  for (const kh::Column &k : c->cols) {
+    (void)hipFree(k.dev);
+    if (k.ckpt) (void)hipFree(k.ckpt);
+  }
   c->cols.clear();
   c->d = kh::DevNodes{};
   c->prep = kh::PrepIn{};
@@ -301,42 +296,56 @@ void free_cols(koordhip_ctx *c) {
   c->n = 0;
 }
 
-template <typename T>
-int upload(koordhip_ctx *c, T *dst, const T *src, size_t count) {
-  if (count == 0) return 0;
-  if (src) {
-    HIP_TRY(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
-  } else {
-    HIP_TRY(hipMemsetAsync(dst, 0, count * sizeof(T), c->stream));
+enum : unsigned { COL_Q = 1, COL_MUT = 2 };  // kh::Column::q, ::mut
+
+// The one place a snapshot column comes to be: allocates it for the c->d.n
+// nodes being loaded, fills it from `host` (NULL: zeros; a COL_Q column's int64
+// quantities through the exact-range gate into f64), records it in c->cols
+// and hands the typed view out.  planes 0: `esize` bytes in all, not per node.
+template <typename V>
+int add_col(koordhip_ctx *c, V *view, const char *name, size_t src, const void *host, unsigned flags = 0,
+            int32_t planes = 1, size_t esize = sizeof(**view)) {
+  kh::Column k{name, nullptr, esize, planes, src, (flags & COL_Q) != 0, (flags & COL_MUT) != 0, nullptr};
+  const size_t bytes = k.bytes(c->d.n);
+  HIP_TRY(hipMalloc(&k.dev, std::max<size_t>(bytes, 1)));
+  c->cols.push_back(k);
+  *view = static_cast<V>(k.dev);
+  if (bytes == 0) return 0;
+  if (!host) {
+    HIP_TRY(hipMemsetAsync(k.dev, 0, bytes, c->stream));
+    return 0;
   }
+  if (!k.q) {
+    HIP_TRY(hipMemcpyAsync(k.dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+    return 0;
+  }
+  const int64_t *q = static_cast<const int64_t *>(host);
+  std::vector<double> tmp(bytes / sizeof(double));
+  for (size_t i = 0; i < tmp.size(); i++) {
+    if (!exact_ok(q[i])) return fail(KOORDHIP_EINVAL, kh::exact_msg(name));
+    tmp[i] = (double)q[i];
+  }
+  HIP_TRY(hipMemcpyAsync(k.dev, tmp.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // tmp goes away
   return 0;
 }
 
-// Resource quantities live on device as exact f64 (eval.hpp): 0 <= v < 2^45.
-// A negative one (no Allocatable, Requested, usage or pod request is) would
-// score above MaxNodeScore in the reference -- beyond the int32 planes for a
-// small capacity, and beyond the totals the ranking bins and keys are sized
-// for -- so it is refused like a too large one.
-constexpr int64_t kExact = 1ll << 45;
+// ... fed by the snapshot's own slot for it (s NULL or the slot NULL: zeros)
+#define SOA_COL(c, s, view, field, ...) \
+  add_col(c, view, #field, offsetof(koordhip_node_soa, field), (s) ? (s)->field : nullptr, ##__VA_ARGS__)
+// ... by slot [i] of a pointer array (alloc[r], numa_free[w], ...)
+#define SOA_COL_AT(c, s, view, field, i, ...)                                                       \
+  add_col(c, view, #field, offsetof(koordhip_node_soa, field) + (size_t)(i) * sizeof(void *),      \
+          (s) ? (s)->field[i] : nullptr, ##__VA_ARGS__)
 
-bool exact_ok(int64_t v) { return v >= 0 && v < kExact; }
-
-// int64 quantity column -> f64 device column (NULL src -> zeros)
-int upload_q(koordhip_ctx *c, double *dst, const int64_t *src, size_t count, const char *what) {
-  if (count == 0) return 0;
-  if (!src) {
-    HIP_TRY(hipMemsetAsync(dst, 0, count * sizeof(double), c->stream));
-    return 0;
-  }
-  std::vector<double> tmp(count);
-  for (size_t i = 0; i < count; i++) {
-    if (!exact_ok(src[i]))
-      return fail(KOORDHIP_EINVAL, std::string(what) + ": quantity outside [0, 2^45), the engine's exact range");
-    tmp[i] = (double)src[i];
-  }
-  HIP_TRY(hipMemcpyAsync(dst, tmp.data(), count * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+// a column's bytes -> host
+int download(const koordhip_ctx *c, const void *dev, void *dst) {
+  for (const kh::Column &k : c->cols)
+    if (k.dev == dev) {
+      if (k.bytes(c->n)) HIP_TRY(hipMemcpy(dst, dev, k.bytes(c->n), hipMemcpyDeviceToHost));
+      return 0;
+    }
+  return fail(KOORDHIP_ESTATE, "not a snapshot column");
 }
 
 // f64 device column -> int64 host array
@@ -597,6 +606,41 @@ int zone_rows(const int64_t *src, const int32_t *cls_of, const uint8_t *flags, c
   return 0;
 }
 
+// The columns every profile reads (validate_soa saw the required ones): Fit,
+// LoadAware and its Filter inputs, the static filters' allow mask.
+int load_base_columns(koordhip_ctx *c, const koordhip_node_soa *s) {
+  kh::DevNodes &d = c->d;
+  kh::PrepIn &pi = c->prep;
+  for (int r = 0; r < KOORDHIP_NRES; r++) {
+    if (int e = SOA_COL_AT(c, s, &d.alloc[r], alloc, r, COL_Q)) return e;
+    if (int e = SOA_COL_AT(c, s, &d.requested[r], requested, r, COL_Q | COL_MUT)) return e;
+  }
+  if (int e = SOA_COL(c, s, &d.alloc_pods, alloc_pods)) return e;
+  if (int e = SOA_COL(c, s, &d.npods, npods, COL_MUT)) return e;
+  if (int e = SOA_COL(c, s, &d.nz_cpu, nz_cpu_m, COL_Q | COL_MUT)) return e;
+  if (int e = SOA_COL(c, s, &d.nz_mem, nz_mem, COL_Q | COL_MUT)) return e;
+  if (int e = SOA_COL(c, s, &d.la_alloc_cpu, la_alloc_cpu_m, COL_Q)) return e;
+  if (int e = SOA_COL(c, s, &d.la_alloc_mem, la_alloc_mem, COL_Q)) return e;
+  if (int e = SOA_COL(c, s, &d.la_used_cpu, la_used_cpu_m, COL_Q | COL_MUT)) return e;
+  if (int e = SOA_COL(c, s, &d.la_used_mem, la_used_mem, COL_Q | COL_MUT)) return e;
+  if (int e = SOA_COL(c, s, &d.la_used_prod_cpu, la_used_prod_cpu_m, COL_Q | COL_MUT)) return e;  // (optional)
+  if (int e = SOA_COL(c, s, &d.la_used_prod_mem, la_used_prod_mem, COL_Q | COL_MUT)) return e;
+  // the status flags launch_prep_flags derives from the LoadAware Filter inputs below
+  if (int e = add_col(c, &d.flags, "flags", kh::kNoSrc, nullptr, COL_MUT)) return e;
+  for (int r = 0; r < 2; r++) {
+    if (int e = SOA_COL_AT(c, s, &pi.used_m[r], laf_used_m, r)) return e;
+    if (int e = SOA_COL_AT(c, s, &pi.total_m[r], laf_total_m, r)) return e;
+    if (int e = SOA_COL_AT(c, s, &pi.prod_used_m[r], laf_prod_used_m, r)) return e;
+    if (int e = SOA_COL_AT(c, s, &pi.thr[r], laf_thr, r)) return e;
+    if (int e = SOA_COL_AT(c, s, &pi.prod_thr[r], laf_prod_thr, r)) return e;
+  }
+  if (int e = SOA_COL(c, s, &pi.la_flags, la_flags)) return e;
+  // static node filters: the allow mask per node (no column = every class)
+  if ((c->dc.filt & KOORDHIP_PLUGIN_NODE_STATIC) && s->static_allow)
+    if (int e = SOA_COL(c, s, &d.sallow, static_allow)) return e;
+  return 0;
+}
+
 int load_numa_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
   kh::DevNuma &nu = c->d.nu;
   nu = kh::DevNuma{};
@@ -624,74 +668,53 @@ int load_numa_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
                          c->stream));
   nu.cls = c->d_classes;
   nu.ncls = c->n_classes;
-  int e = 0;
-  int32_t *nc = nullptr, *cnt = nullptr;
-  uint8_t *nf = nullptr;
-  e = dev_alloc(c, &nc, n);
-  if (!e) {
-    if (have) {
-      e = upload(c, nc, s->numa_class, n);
-    } else if (n) {
-      std::vector<int32_t> none(n, -1);  // no NodeResourceTopology anywhere
-      HIP_TRY(hipMemcpyAsync(nc, none.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-      HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+  // a NUMA or Reservation profile on a snapshot without NUMA columns: zero
+  // columns, and no NodeResourceTopology anywhere
+  const koordhip_node_soa *ns = have ? s : nullptr;
+  const unsigned mut = c->numa ? COL_MUT : 0;  // (under Reservation alone nothing advances them)
+  const std::vector<int32_t> none(have ? 0 : n, -1);
+  if (int e = add_col(c, &nu.node_cls, "numa_class", offsetof(koordhip_node_soa, numa_class),
+                      have ? s->numa_class : none.data()))
+    return e;
+  if (!have) HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int e = SOA_COL(c, ns, &nu.cnt, numa_alloc_cnt, mut)) return e;
+  if (int e = SOA_COL(c, ns, &nu.nflags, numa_flags)) return e;
+  for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) {
+    if (int e = SOA_COL_AT(c, ns, &nu.fr[w], numa_free, w, mut)) return e;
+    if (int e = SOA_COL_AT(c, ns, &nu.ep[w], numa_excl_pcpu, w, mut)) return e;
+    if (int e = SOA_COL_AT(c, ns, &nu.en[w], numa_excl_numa, w, mut)) return e;
   }
-  if (!e) e = dev_alloc(c, &cnt, n);
-  if (!e) e = upload(c, cnt, have ? s->numa_alloc_cnt : nullptr, n);
-  if (!e) e = dev_alloc(c, &nf, n);
-  if (!e) e = upload(c, nf, have ? s->numa_flags : nullptr, n);
-  for (int w = 0; w < KOORDHIP_NUMA_WORDS && !e; w++) {
-    uint64_t *a = nullptr, *b = nullptr, *d = nullptr;
-    e = dev_alloc(c, &a, n);
-    if (!e) e = upload(c, a, have ? s->numa_free[w] : nullptr, n);
-    if (!e) e = dev_alloc(c, &b, n);
-    if (!e) e = upload(c, b, have ? s->numa_excl_pcpu[w] : nullptr, n);
-    if (!e) e = dev_alloc(c, &d, n);
-    if (!e) e = upload(c, d, have ? s->numa_excl_numa[w] : nullptr, n);
-    nu.fr[w] = a;
-    nu.ep[w] = b;
-    nu.en[w] = d;
-  }
-  nu.node_cls = nc;
-  nu.cnt = cnt;
-  nu.nflags = nf;
   // NUMA zones: kept when the snapshot carries the columns (a later
   // update_nodes may give a node a topology policy); zones mode once any
   // node has a policy
   bool any = false;
   c->dc.zones = 0;
-  if (!e && have) {
+  if (have) {
     std::vector<double> za, zu;
-    e = zone_rows(s->numa_zone_alloc, s->numa_class, s->numa_flags, cls.data(), n, za, &any);
-    if (!e) e = zone_rows(s->numa_zone_used, s->numa_class, s->numa_flags, cls.data(), n, zu, &any);
-    if (!e && s->numa_zone_alloc && s->numa_zone_used) {
+    if (int e = zone_rows(s->numa_zone_alloc, s->numa_class, s->numa_flags, cls.data(), n, za, &any)) return e;
+    if (int e = zone_rows(s->numa_zone_used, s->numa_class, s->numa_flags, cls.data(), n, zu, &any)) return e;
+    if (s->numa_zone_alloc && s->numa_zone_used) {
       // rows of nodes without a policy are never read: converted as zeros
-      double *a = nullptr, *u = nullptr;
-      e = dev_alloc(c, &a, (size_t)n * 2 * KOORDHIP_NUMA_MAX_ZONES);
-      if (!e) e = dev_alloc(c, &u, (size_t)n * 2 * KOORDHIP_NUMA_MAX_ZONES);
-      if (!e) e = upload(c, a, za.data(), za.size());
-      if (!e) e = upload(c, u, zu.data(), zu.size());
-      if (!e) HIP_TRY(hipStreamSynchronize(c->stream));
-      nu.za = a;
-      nu.zu = u;
+      if (int e = add_col(c, &nu.za, "numa_zone_alloc", offsetof(koordhip_node_soa, numa_zone_alloc), za.data(), 0, 1,
+                          sizeof(kh::ZoneRow)))
+        return e;
+      if (int e = add_col(c, &nu.zu, "numa_zone_used", offsetof(koordhip_node_soa, numa_zone_used), zu.data(), mut, 1,
+                          sizeof(kh::ZoneRow)))
+        return e;
+      HIP_TRY(hipStreamSynchronize(c->stream));
     }
     c->dc.zones = any ? 1 : 0;
   }
   // CPU amplification ratios (kept whenever the snapshot carries the column)
   c->dc.amp = 0;
-  if (!e && have && s->numa_amp_cpu) {
+  if (have && s->numa_amp_cpu) {
     bool any_amp = false;
-    e = check_amp(s->numa_amp_cpu, s->numa_flags, n, &any_amp);
-    double *a = nullptr;
-    if (!e) e = dev_alloc(c, &a, (size_t)n);
-    if (!e) e = upload(c, a, s->numa_amp_cpu, (size_t)n);
-    if (!e) HIP_TRY(hipStreamSynchronize(c->stream));
-    nu.amp = a;
+    if (int e = check_amp(s->numa_amp_cpu, s->numa_flags, n, &any_amp)) return e;
+    if (int e = SOA_COL(c, s, &nu.amp, numa_amp_cpu)) return e;
     c->dc.amp = any_amp ? 1 : 0;
   }
   c->host_classes = cls;
-  return e;
+  return 0;
 }
 
 // Reservation columns (resv_slots Available reservations per node, slot-major):
@@ -727,7 +750,7 @@ int check_resv_cpus(const koordhip_node_soa *s, int32_t m, int32_t slots, const 
       uint64_t any = 0;
       for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) any |= s->resv_cpus[w][at];
       if (!any) continue;
-      if (!(s->resv_flags[at] & KOORDHIP_RESV_PRESENT))
+      if (!s->resv_flags || !(s->resv_flags[at] & KOORDHIP_RESV_PRESENT))  // (no reservation columns: every slot is empty)
         return fail(KOORDHIP_EINVAL, "resv_cpus on an empty reservation slot");
       const int32_t cls = s->numa_class ? s->numa_class[i] : -1;
       if (cls < 0 || cls >= nclasses) return fail(KOORDHIP_EINVAL, "resv_cpus on a node without a CPU topology");
@@ -754,71 +777,36 @@ int load_resv_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
   // a snapshot without reservation columns gets zero columns: the Reservation
   // build (NM 3) still runs the plugin, e.g. a pod with a required reservation
   // affinity fails its Filter on every node (plugin.go:378-381)
-  std::vector<uint32_t> zf;
-  std::vector<int32_t> zi;
-  std::vector<int64_t> zq;
-  koordhip_node_soa zs;
-  if (!s->resv_flags) {
-    zf.assign(std::max(n, 1), 0u);
-    zi.assign(std::max(n, 1), 0);
-    zq.assign(std::max(n, 1), 0);
-    zs = *s;
-    zs.resv_flags = zf.data();
-    zs.resv_order_rank = zi.data();
-    zs.resv_assigned = zi.data();
-    for (int k = 0; k < 2; k++) zs.resv_alloc[k] = zs.resv_nz[k] = zs.resv_allocated[k] = zq.data();
-    s = &zs;
-  }
-  const int32_t slots = std::max(1, s->resv_slots);
-  const int32_t sn = slots * n;  // slot-major columns
-  if (int e = check_resv_rows(s, sn)) return e;
+  const koordhip_node_soa *rs = s->resv_flags ? s : nullptr;
+  const int32_t slots = std::max(1, s->resv_slots);  // slot-major columns: `slots` planes each
+  if (rs)
+    if (int e = check_resv_rows(rs, slots * n)) return e;
   kh::DevResv &rv = c->d.rv;
-  uint32_t *f = nullptr;
-  int32_t *rk = nullptr, *rn = nullptr;
-  int e = dev_alloc(c, &f, sn);
-  if (!e) e = upload(c, f, s->resv_flags, sn);
-  if (!e) e = dev_alloc(c, &rk, sn);
-  if (!e) e = upload(c, rk, s->resv_order_rank, sn);
-  if (!e) e = dev_alloc(c, &rn, sn);
-  if (!e) e = upload(c, rn, s->resv_assigned, sn);
-  for (int k = 0; k < 2 && !e; k++) {
-    double *a = nullptr, *z = nullptr, *d = nullptr;
-    e = dev_alloc(c, &a, sn);
-    if (!e) e = upload_q(c, a, s->resv_alloc[k], sn, "resv_alloc");
-    if (!e) e = dev_alloc(c, &z, sn);
-    if (!e) e = upload_q(c, z, s->resv_nz[k], sn, "resv_nz");
-    if (!e) e = dev_alloc(c, &d, sn);
-    if (!e) e = upload_q(c, d, s->resv_allocated[k], sn, "resv_allocated");
-    rv.ra[k] = a;
-    rv.rz[k] = z;
-    rv.rd[k] = d;
+  if (int e = SOA_COL(c, rs, &rv.flags, resv_flags, 0, slots)) return e;
+  if (int e = SOA_COL(c, rs, &rv.rank, resv_order_rank, 0, slots)) return e;
+  if (int e = SOA_COL(c, rs, &rv.rn, resv_assigned, COL_MUT, slots)) return e;
+  for (int k = 0; k < 2; k++) {
+    if (int e = SOA_COL_AT(c, rs, &rv.ra[k], resv_alloc, k, COL_Q, slots)) return e;
+    if (int e = SOA_COL_AT(c, rs, &rv.rz[k], resv_nz, k, COL_Q, slots)) return e;
+    if (int e = SOA_COL_AT(c, rs, &rv.rd[k], resv_allocated, k, COL_Q | COL_MUT, slots)) return e;
   }
   // the reserved CPUs left per slot (NodeNUMAResource RestoreReservation)
   c->dc.resv_cpus = 0;
-  if (!e && s->resv_cpus[0] && c->numa) {  // (without NodeNUMAResource nothing reads them)
+  if (s->resv_cpus[0] && c->numa) {  // (without NodeNUMAResource nothing reads them)
     for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++)
-      if (!s->resv_cpus[w]) e = fail(KOORDHIP_EINVAL, "resv_cpus: every word column or none");
+      if (!s->resv_cpus[w]) return fail(KOORDHIP_EINVAL, "resv_cpus: every word column or none");
     std::vector<int32_t> ncpu;
     for (int32_t k = 0; k < s->n_numa_classes && s->numa_classes; k++) ncpu.push_back(s->numa_classes[k].num_cpus);
-    if (!e) e = check_resv_cpus(s, n, slots, ncpu);
-    for (int w = 0; w < KOORDHIP_NUMA_WORDS && !e; w++) {
-      uint64_t *m = nullptr;
-      e = dev_alloc(c, &m, sn);
-      if (!e) e = upload(c, m, s->resv_cpus[w], sn);
-      rv.rc[w] = m;
-    }
-    if (!e) c->dc.resv_cpus = 1;
+    if (int e = check_resv_cpus(s, n, slots, ncpu)) return e;
+    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++)
+      if (int e = SOA_COL_AT(c, s, &rv.rc[w], resv_cpus, w, COL_MUT, slots)) return e;
+    c->dc.resv_cpus = 1;
   }
-  rv.flags = f;
-  rv.rank = rk;
-  rv.rn = rn;
   rv.slots = slots;
   rv.stride = n;
-  if (!e) {
-    c->dc.resv = 1;
-    c->dc.resv_slots = slots;
-  }
-  return e;
+  c->dc.resv = 1;
+  c->dc.resv_slots = slots;
+  return 0;
 }
 
 // The device-holding reservation columns of a snapshot or of update rows (m
@@ -875,6 +863,51 @@ int check_resv_scalars(const int64_t *xa, const int64_t *xd, const int32_t *slot
   return 0;
 }
 
+// The DeviceShare device rows of a snapshot or of update rows (m rows of
+// s->dev_slots minors per type; `pre` heads the message).
+int check_dev_rows(const koordhip_node_soa *s, int32_t m, const char *pre) {
+  const std::string p(pre);
+  const size_t ms = (size_t)m * KOORDHIP_DEV_TYPES * s->dev_slots;
+  // the scorer's percent quotients (dev.hpp dev_pct_div: an f64 reciprocal and
+  // one exact fix-up) equal Go's int64 division only for operands below 2^45
+  for (size_t a = 0; a < ms * KOORDHIP_DEV_RES; a++)
+    if (!exact_ok(s->dev_total[a]) || (s->dev_used && !exact_ok(s->dev_used[a])))
+      return fail(KOORDHIP_EINVAL, p + "dev_total / dev_used out of [0, 2^45)");
+  // a node holds one GPU model: every GPU with resources has the same memory
+  // (fillGPUTotalMem reads the first one, utils.go:211-233)
+  for (int32_t i = 0; i < m; i++) {
+    int64_t mem = -1;
+    for (int32_t q = 0; q < s->dev_slots; q++) {
+      const size_t a = ((size_t)i * KOORDHIP_DEV_TYPES + KOORDHIP_DEV_GPU) * s->dev_slots + q;
+      if (s->dev_minor[a] < 0) continue;
+      const int64_t *t = s->dev_total + a * KOORDHIP_DEV_RES;
+      if (t[0] == 0 && t[1] == 0 && t[2] == 0) continue;
+      if (t[2] <= 0) return fail(KOORDHIP_EINVAL, p + "a GPU with resources but no gpu-memory");
+      if (mem >= 0 && t[2] != mem) return fail(KOORDHIP_EINVAL, p + "GPUs of different memory sizes on one node");
+      mem = t[2];
+    }
+  }
+  return 0;
+}
+
+// The topology domains [keys][m] of a snapshot or of update rows: -1 (no
+// label) or a domain of the key -- below ndom[k] (NULL: KOORDHIP_PTS_DOMAINS),
+// for a hostname key (bit k of host) the row's own node, which is node[j]
+// (NULL: j) of the snapshot's n.
+int check_pts_dom(const int32_t *dom, int32_t keys, int32_t m, uint32_t host, int32_t n, const int32_t *ndom,
+                  const int32_t *node, const char *pre) {
+  for (int k = 0; k < keys; k++) {
+    const bool hostname = (host >> k) & 1u;
+    const int32_t hi = hostname ? n : (ndom ? ndom[k] : KOORDHIP_PTS_DOMAINS);
+    for (int32_t j = 0; j < m; j++) {
+      const int32_t v = dom[(size_t)k * m + j];
+      if (v < -1 || v >= hi || (hostname && v >= 0 && v != (node ? node[j] : j)))
+        return fail(KOORDHIP_EINVAL, std::string(pre) + "pts_dom out of range (a hostname domain is the node)");
+    }
+  }
+  return 0;
+}
+
 // ABI 9 columns of the sequential cycle: DeviceShare devices, extended
 // scalars, static Scores (int64 on device: the device code is integer).
 int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
@@ -888,93 +921,42 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
                                    "PodTopologySpread or a normalized Score plugin in the profile (the sequential cycle)");
     return 0;
   }
-  int e = 0;
   if (dev && s->dev_slots > 0) {
     if (s->dev_slots > KOORDHIP_DEV_SLOTS || !s->dev_present || !s->dev_minor || !s->dev_total)
       return fail(KOORDHIP_EINVAL, "dev_slots > KOORDHIP_DEV_SLOTS or a device column missing");
-    const size_t ns = (size_t)n * KOORDHIP_DEV_TYPES * s->dev_slots;
-    // the scorer's percent quotients (dev.hpp dev_pct_div: an f64 reciprocal and
-    // one exact fix-up) equal Go's int64 division only for operands below 2^45
-    for (size_t a = 0; a < ns * KOORDHIP_DEV_RES; a++)
-      if (s->dev_total[a] < 0 || s->dev_total[a] >= (1ll << 45) ||
-          (s->dev_used && (s->dev_used[a] < 0 || s->dev_used[a] >= (1ll << 45))))
-        return fail(KOORDHIP_EINVAL, "dev_total / dev_used out of [0, 2^45)");
-    // a node holds one GPU model: every GPU with resources has the same memory
-    // (fillGPUTotalMem reads the first one, utils.go:211-233)
-    for (int32_t i = 0; i < n; i++) {
-      int64_t mem = -1;
-      for (int32_t q = 0; q < s->dev_slots; q++) {
-        const size_t a = ((size_t)i * KOORDHIP_DEV_TYPES + KOORDHIP_DEV_GPU) * s->dev_slots + q;
-        if (s->dev_minor[a] < 0) continue;
-        const int64_t *t = s->dev_total + a * KOORDHIP_DEV_RES;
-        if (t[0] == 0 && t[1] == 0 && t[2] == 0) continue;
-        if (t[2] <= 0) return fail(KOORDHIP_EINVAL, "a GPU with resources but no gpu-memory");
-        if (mem >= 0 && t[2] != mem) return fail(KOORDHIP_EINVAL, "GPUs of different memory sizes on one node");
-        mem = t[2];
-      }
-    }
-    uint8_t *pr = nullptr;
-    int32_t *mi = nullptr;
-    int64_t *tt = nullptr, *us = nullptr;
-    e = dev_alloc(c, &pr, n);
-    if (!e) e = upload(c, pr, s->dev_present, n);
-    if (!e) e = dev_alloc(c, &mi, ns);
-    if (!e) e = upload(c, mi, s->dev_minor, ns);
-    if (!e) e = dev_alloc(c, &tt, ns * KOORDHIP_DEV_RES);
-    if (!e) e = upload(c, tt, s->dev_total, ns * KOORDHIP_DEV_RES);
-    if (!e) e = dev_alloc(c, &us, ns * KOORDHIP_DEV_RES);
-    if (!e) e = upload(c, us, s->dev_used, ns * KOORDHIP_DEV_RES);  // NULL: zeros
+    if (int e = check_dev_rows(s, n, "")) return e;
+    // a node's whole device row is one element
+    const size_t minors = sizeof(int32_t) * KOORDHIP_DEV_TYPES * s->dev_slots, row = minors * 2 * KOORDHIP_DEV_RES;
     dv.slots = s->dev_slots;
-    dv.present = pr;
-    dv.minor = mi;
-    dv.total = tt;
-    dv.used = us;
+    if (int e = SOA_COL(c, s, &dv.present, dev_present)) return e;
+    if (int e = SOA_COL(c, s, &dv.minor, dev_minor, 0, 1, minors)) return e;
+    if (int e = SOA_COL(c, s, &dv.total, dev_total, 0, 1, row)) return e;
+    if (int e = SOA_COL(c, s, &dv.used, dev_used, COL_MUT, 1, row)) return e;
     // DeviceShare's reservation restore (deviceshare/reservation.go:119-170):
     // each node's one reservation holding devices
-    if (!e && s->resv_dev_slot && s->resv_dev) {
-      if (int ce = check_resv_dev(s, n)) return ce;
-      const size_t per = (size_t)KOORDHIP_DEV_TYPES * s->dev_slots * KOORDHIP_DEV_RES;
-      int32_t *rs = nullptr;
-      int64_t *rd = nullptr;
-      e = dev_alloc(c, &rs, n);
-      if (!e) e = upload(c, rs, s->resv_dev_slot, n);
-      if (!e) e = dev_alloc(c, &rd, (size_t)n * 2 * per);
-      if (!e) e = upload(c, rd, s->resv_dev, (size_t)n * 2 * per);
-      dv.rslot = rs;
-      dv.rdev = rd;
+    if (s->resv_dev_slot && s->resv_dev) {
+      if (int e = check_resv_dev(s, n)) return e;
+      if (int e = SOA_COL(c, s, &dv.rslot, resv_dev_slot)) return e;
+      if (int e = SOA_COL(c, s, &dv.rdev, resv_dev, COL_MUT, 1, 2 * row)) return e;
       // ABI 14: that reservation's extended scalars (Allocatable, Allocated)
-      if (!e && s->resv_xalloc) {
-        if (int xe = check_resv_scalars(s->resv_xalloc, s->resv_xallocated, s->resv_dev_slot, n)) return xe;
-        int64_t *xa = nullptr, *xd = nullptr;
-        e = dev_alloc(c, &xa, (size_t)n * KOORDHIP_NXRES);
-        if (!e) e = upload(c, xa, s->resv_xalloc, (size_t)n * KOORDHIP_NXRES);
-        if (!e) e = dev_alloc(c, &xd, (size_t)n * KOORDHIP_NXRES);
-        if (!e) e = upload(c, xd, s->resv_xallocated, (size_t)n * KOORDHIP_NXRES);  // NULL: zeros
-        dv.rxa = xa;
-        dv.rxd = xd;
+      if (s->resv_xalloc) {
+        if (int e = check_resv_scalars(s->resv_xalloc, s->resv_xallocated, s->resv_dev_slot, n)) return e;
+        if (int e = SOA_COL(c, s, &dv.rxa, resv_xalloc, 0, KOORDHIP_NXRES)) return e;
+        if (int e = SOA_COL(c, s, &dv.rxd, resv_xallocated, COL_MUT, KOORDHIP_NXRES)) return e;
         for (size_t a = 0; a < (size_t)n * KOORDHIP_NXRES && !c->resv_x; a++) c->resv_x = s->resv_xalloc[a] != 0;
       }
     }
   }
-  if (!e && s->resv_xalloc && !dv.rxa)
+  if (s->resv_xalloc && !dv.rxa)
     return fail(KOORDHIP_EINVAL, "resv_xalloc needs DeviceShare and the device-holding reservation columns "
                                  "(resv_dev_slot, resv_dev)");
-  int64_t *xa = nullptr, *xr = nullptr;
-  if (!e && s->xalloc) {
-    e = dev_alloc(c, &xa, (size_t)n * KOORDHIP_NXRES);
-    if (!e) e = upload(c, xa, s->xalloc, (size_t)n * KOORDHIP_NXRES);
-  }
-  if (!e) e = dev_alloc(c, &xr, (size_t)n * KOORDHIP_NXRES);
-  if (!e) e = upload(c, xr, s->xrequested, (size_t)n * KOORDHIP_NXRES);
-  dv.xalloc = xa;
-  dv.xreq = xr;
-  for (int w = 0; w < 2 && !e; w++) {
+  if (s->xalloc)
+    if (int e = SOA_COL(c, s, &dv.xalloc, xalloc, 0, KOORDHIP_NXRES)) return e;
+  if (int e = SOA_COL(c, s, &dv.xreq, xrequested, COL_MUT, KOORDHIP_NXRES)) return e;
+  for (int w = 0; w < 2; w++) {
     const uint32_t bit = w == 0 ? KOORDHIP_PLUGIN_AFFINITY_SCORE : KOORDHIP_PLUGIN_TAINT_SCORE;
     if (!(c->cfg.score_plugins & bit) || !s->static_score[w]) continue;
-    uint16_t *ss = nullptr;
-    e = dev_alloc(c, &ss, (size_t)n * KOORDHIP_MAX_STATIC_CLASSES);
-    if (!e) e = upload(c, ss, s->static_score[w], (size_t)n * KOORDHIP_MAX_STATIC_CLASSES);
-    dv.sscore[w] = ss;
+    if (int e = SOA_COL_AT(c, s, &dv.sscore[w], static_score, w, 0, KOORDHIP_MAX_STATIC_CLASSES)) return e;
   }
   // PodTopologySpread: the keys' domains, the constraint table's counts, the classes' eligibility
   c->pts = kh::PtsArgs{};
@@ -983,7 +965,7 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
   const bool pts = ((c->cfg.filter_plugins | c->cfg.score_plugins) & KOORDHIP_PLUGIN_PTS) != 0;
   const bool ipa = ((c->cfg.filter_plugins | c->cfg.score_plugins) & KOORDHIP_PLUGIN_IPA) != 0;
   // (the topology keys serve both plugins: loaded when either runs)
-  if (!e && (pts || ipa) && s->pts_keys > 0) {
+  if ((pts || ipa) && s->pts_keys > 0) {
     if (s->pts_keys > KOORDHIP_PTS_KEYS || s->pts_cons < 0 || s->pts_cons > KOORDHIP_PTS_CONS || s->pts_classes < 0 ||
         s->pts_classes > KOORDHIP_PTS_CLASSES || !s->pts_dom || !s->pts_elig || (s->pts_cons > 0 && !s->pts_cnt))
       return fail(KOORDHIP_EINVAL, "PodTopologySpread tables outside KOORDHIP_PTS_* or a column missing");
@@ -993,25 +975,15 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
     for (int cc = 0; cc < s->pts_cons; cc++)
       if (s->pts_cons_key[cc] < 0 || s->pts_cons_key[cc] >= s->pts_keys)
         return fail(KOORDHIP_EINVAL, "PodTopologySpread: a constraint's key is out of range");
-    for (int k = 0; k < s->pts_keys; k++)
-      for (int32_t i = 0; i < n; i++) {
-        const int32_t v = s->pts_dom[(size_t)k * n + i];
-        const int32_t hi = ((s->pts_hostname >> k) & 1u) ? n : s->pts_ndom[k];
-        if (v < -1 || v >= hi || (((s->pts_hostname >> k) & 1u) && v >= 0 && v != i))
-          return fail(KOORDHIP_EINVAL, "PodTopologySpread: pts_dom out of range (a hostname domain is the node)");
-      }
-    int32_t *pd = nullptr, *pc = nullptr;
-    uint16_t *pe = nullptr;
-    e = dev_alloc(c, &pd, (size_t)n * s->pts_keys);
-    if (!e) e = upload(c, pd, s->pts_dom, (size_t)n * s->pts_keys);
-    if (!e) e = dev_alloc(c, &pc, (size_t)n * std::max(1, s->pts_cons));
-    if (!e) e = upload(c, pc, s->pts_cons > 0 ? s->pts_cnt : nullptr, (size_t)n * std::max(1, s->pts_cons));
-    if (!e) e = dev_alloc(c, &pe, (size_t)n);
-    if (!e) e = upload(c, pe, s->pts_elig, (size_t)n);
+    if (int e = check_pts_dom(s->pts_dom, s->pts_keys, n, s->pts_hostname, n, s->pts_ndom, nullptr, "PodTopologySpread: "))
+      return e;
     kh::PtsArgs &pa = c->pts;
-    pa.dom = pd;
-    pa.cnt = pc;
-    pa.elig = pe;
+    if (int e = SOA_COL(c, s, &pa.dom, pts_dom, 0, s->pts_keys)) return e;
+    // (a table without constraints keeps one plane of zeros)
+    if (int e = add_col(c, &pa.cnt, "pts_cnt", offsetof(koordhip_node_soa, pts_cnt), s->pts_cons > 0 ? s->pts_cnt : nullptr,
+                        COL_MUT, std::max(1, s->pts_cons)))
+      return e;
+    if (int e = SOA_COL(c, s, &pa.elig, pts_elig)) return e;
     pa.keys = s->pts_keys;
     pa.cons = s->pts_cons;
     pa.classes = s->pts_classes;
@@ -1021,7 +993,7 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
     for (int cc = 0; cc < KOORDHIP_PTS_CONS; cc++) pa.cons_key[cc] = cc < s->pts_cons ? s->pts_cons_key[cc] : 0;
   }
   // InterPodAffinity: the count entries over those keys
-  if (!e && ipa && s->ipa_ents > 0) {
+  if (ipa && s->ipa_ents > 0) {
     if (s->ipa_ents > KOORDHIP_IPA_ENTRIES || !s->ipa_cnt || !c->pts.dom)
       return fail(KOORDHIP_EINVAL, "InterPodAffinity: more than KOORDHIP_IPA_ENTRIES entries, ipa_cnt missing, or no "
                                    "topology keys (pts_keys / pts_dom)");
@@ -1039,14 +1011,10 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
       most = std::max(most, tot);
     }
     c->ipa_pods_bound = most;
-    int32_t *ic = nullptr, *sums = nullptr;
-    e = dev_alloc(c, &ic, (size_t)n * s->ipa_ents);
-    if (!e) e = upload(c, ic, s->ipa_cnt, (size_t)n * s->ipa_ents);
-    if (!e) e = dev_alloc(c, &sums, (size_t)kh::IPA_SUMS);
     kh::IpaArgs &ia = c->ipa;
     ia.dom = c->pts.dom;
-    ia.cnt = ic;
-    ia.sums = sums;
+    if (int e = SOA_COL(c, s, &ia.cnt, ipa_cnt, COL_MUT, s->ipa_ents)) return e;
+    if (int e = add_col(c, &ia.sums, "ipa.sums", kh::kNoSrc, nullptr, 0, 0, sizeof(int32_t) * kh::IPA_SUMS)) return e;
     ia.ents = s->ipa_ents;
     ia.host = s->pts_hostname;
     ia.filt = (c->cfg.filter_plugins & KOORDHIP_PLUGIN_IPA) ? 1 : 0;
@@ -1058,7 +1026,7 @@ int load_ext_columns(koordhip_ctx *c, const koordhip_node_soa *s, int32_t n) {
   // (a profile scoring PodTopologySpread on a snapshot without tables: every
   // node scores 100, as for pods without constraints)
   if (pts && !c->pts.dom) c->pts.score = (c->cfg.score_plugins & KOORDHIP_PLUGIN_PTS) ? 1 : 0;
-  return e;
+  return 0;
 }
 
 int pipe_status(koordhip_ctx *c);
@@ -1293,7 +1261,6 @@ int koordhip_destroy(koordhip_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   free_cols(c);
-  for (void *p : c->ckpt) (void)hipFree(p);
   for (void *p : {(void *)c->d_pods, (void *)c->d_out, (void *)c->d_partial[0], (void *)c->d_partial[1], (void *)c->d_lists,
                   (void *)c->d_gather, (void *)c->d_final, (void *)c->d_tmp_pod, (void *)c->d_tmp_podx, (void *)c->d_dbg,
                   (void *)c->d_cpus, (void *)c->d_classes, (void *)c->d_rc, (void *)c->d_mod, (void *)c->d_desc,
@@ -1348,75 +1315,11 @@ int koordhip_load_snapshot(koordhip_ctx *c, const koordhip_node_soa *s, int32_t 
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->diag_valid = false;
   c->pre_loaded = false;
-  free_cols(c);
-  for (void *p : c->ckpt) (void)hipFree(p);
-  c->ckpt.clear();
+  free_cols(c);  // (the previous snapshot and its checkpoint: a refused load leaves none)
   kh::DevNodes &d = c->d;
-  d.n = n;
-  int e = 0;
-  for (int r = 0; r < KOORDHIP_NRES && !e; r++) {
-    double *a = nullptr, *q = nullptr;
-    e = dev_alloc(c, &a, n);
-    if (!e) e = dev_alloc(c, &q, n);
-    if (!e) e = upload_q(c, a, s->alloc[r], n, "alloc");
-    if (!e) e = upload_q(c, q, s->requested[r], n, "requested");
-    d.alloc[r] = a;
-    d.requested[r] = q;
-  }
-  auto col64 = [&](int64_t **dst, const int64_t *src) {
-    if (!e) e = dev_alloc(c, dst, n);
-    if (!e) e = upload(c, *dst, src, n);
-  };
-  auto colq = [&](double **dst, const int64_t *src, const char *what) {
-    if (!e) e = dev_alloc(c, dst, n);
-    if (!e) e = upload_q(c, *dst, src, n, what);
-  };
-  int32_t *ap = nullptr, *np = nullptr;
-  if (!e) e = dev_alloc(c, &ap, n);
-  if (!e) e = upload(c, ap, s->alloc_pods, n);
-  if (!e) e = dev_alloc(c, &np, n);
-  if (!e) e = upload(c, np, s->npods, n);
-  d.alloc_pods = ap;
-  d.npods = np;
-  colq(&d.nz_cpu, s->nz_cpu_m, "nz_cpu_m");
-  colq(&d.nz_mem, s->nz_mem, "nz_mem");
-  double *lac = nullptr, *lam = nullptr;
-  colq(&lac, s->la_alloc_cpu_m, "la_alloc_cpu_m");
-  colq(&lam, s->la_alloc_mem, "la_alloc_mem");
-  d.la_alloc_cpu = lac;
-  d.la_alloc_mem = lam;
-  colq(&d.la_used_cpu, s->la_used_cpu_m, "la_used_cpu_m");
-  colq(&d.la_used_mem, s->la_used_mem, "la_used_mem");
-  colq(&d.la_used_prod_cpu, s->la_used_prod_cpu_m, "la_used_prod_cpu_m");  // NULL -> zeros
-  colq(&d.la_used_prod_mem, s->la_used_prod_mem, "la_used_prod_mem");
-  if (!e) e = dev_alloc(c, &d.flags, n);
-  // LoadAware Filter inputs
   kh::PrepIn &pi = c->prep;
-  for (int r = 0; r < 2 && !e; r++) {
-    int64_t *a = nullptr, *b = nullptr, *cc = nullptr, *t = nullptr, *pt = nullptr;
-    col64(&a, s->laf_used_m[r]);
-    col64(&b, s->laf_total_m[r]);
-    col64(&cc, s->laf_prod_used_m[r]);
-    col64(&t, s->laf_thr[r]);
-    col64(&pt, s->laf_prod_thr[r]);
-    pi.used_m[r] = a;
-    pi.total_m[r] = b;
-    pi.prod_used_m[r] = cc;
-    pi.thr[r] = t;
-    pi.prod_thr[r] = pt;
-  }
-  uint8_t *lf = nullptr;
-  if (!e) e = dev_alloc(c, &lf, n);
-  if (!e) e = upload(c, lf, s->la_flags, n);
-  pi.la_flags = lf;
-  // static node filters: the allow mask per node (no column = every class)
-  d.sallow = nullptr;
-  if (!e && (c->dc.filt & KOORDHIP_PLUGIN_NODE_STATIC) && s->static_allow) {
-    uint32_t *sa = nullptr;
-    e = dev_alloc(c, &sa, n);
-    if (!e) e = upload(c, sa, s->static_allow, n);
-    d.sallow = sa;
-  }
+  d.n = n;
+  int e = load_base_columns(c, s);
   if (!e) e = load_numa_columns(c, s, n);
   if (!e) e = load_resv_columns(c, s, n);
   if (!e) e = load_ext_columns(c, s, n);
@@ -1459,12 +1362,7 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
       return fail(KOORDHIP_EINVAL, "duplicate row index (a row would mix fields of two updates)");
   }
-  // device-holding reservations (ABI 13 / 14): a row carrying the reservation
-  // columns replaces ALL of the node's reservation state, its device-holding
-  // reservation included -- rows without resv_dev_slot / resv_dev (and
-  // resv_xalloc) hold none, so the node's slot, device allocation and scalars
-  // are cleared (a different reservation moving into the slot cannot inherit
-  // them).  Rows without reservation columns leave all of it alone.
+  // device-holding reservations (ABI 13 / 14) of the rows
   const bool rdev_rows = rows->resv_dev_slot || rows->resv_dev || rows->resv_xalloc || rows->resv_xallocated;
   if (rdev_rows) {
     if (!c->d.dv.rslot)
@@ -1513,14 +1411,11 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
                                    "again (such snapshots run in the sequential cycle)");
     zrows = zrows && c->d.nu.za;
   }
-  bool amp_rows = false, amp_any = false;
+  bool amp_any = false;
   if (numa_rows && rows->numa_amp_cpu) {
     if (int e = check_amp(rows->numa_amp_cpu, rows->numa_flags, m, &amp_any)) return e;
-    if (!c->d.nu.amp) {
-      bool any = amp_any;
-      if (any) return fail(KOORDHIP_EINVAL, "a CPU amplification ratio needs the numa_amp_cpu column at load_snapshot");
-    }
-    amp_rows = c->d.nu.amp != nullptr;
+    if (amp_any && !c->d.nu.amp)
+      return fail(KOORDHIP_EINVAL, "a CPU amplification ratio needs the numa_amp_cpu column at load_snapshot");
   }
   if ((c->dc.filt & KOORDHIP_PLUGIN_NODE_STATIC) && rows->static_allow && !c->d.sallow)
     for (int32_t j = 0; j < m; j++)
@@ -1538,223 +1433,113 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
   if (resv_rows)
     if (int e = check_resv_rows(rows, rslots * m)) return e;
   // reserved CPUs of the rows (NULL: none), only into a snapshot loaded with them
-  std::vector<uint64_t> zero_rc;
-  const uint64_t *rc_rows[KOORDHIP_NUMA_WORDS] = {};
-  if (resv_rows && c->numa && rows->resv_cpus[0]) {
+  const bool rc_rows = resv_rows && c->numa && rows->resv_cpus[0];
+  if (rc_rows) {
     for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++)
       if (!rows->resv_cpus[w]) return fail(KOORDHIP_EINVAL, "resv_cpus: every word column or none");
     if (!numa_rows) return fail(KOORDHIP_EINVAL, "update rows with resv_cpus need the NUMA columns");
     std::vector<int32_t> ncpu;
     for (const auto &k : c->host_classes) ncpu.push_back(k.ncpu);
     if (int e = check_resv_cpus(rows, m, rslots, ncpu)) return e;
-    if (!c->dc.resv_cpus) {
+    if (!c->dc.resv_cpus)
       for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++)
         for (int32_t j = 0; j < rslots * m; j++)
           if (rows->resv_cpus[w][j]) return fail(KOORDHIP_EINVAL, "reserved CPUs need the resv_cpus columns at load_snapshot");
-    } else {
-      for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) rc_rows[w] = rows->resv_cpus[w];
-    }
-  } else if (resv_rows && c->dc.resv_cpus) {
-    zero_rc.assign((size_t)rslots * (size_t)m, 0ull);
-    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) rc_rows[w] = zero_rc.data();
   }
-  // ---- one host staging image: [idx][column 0][column 1]..., 8-B aligned
-  //      segments, quantities converted to the device's exact f64
-  struct Col {
-    void *dst;
-    const void *src;
-    int32_t esize;  // 8, 4 or 1 (or a whole ZoneRow)
-    bool q;         // int64 quantity -> f64
-    const char *what;
-  };
-  kh::DevNodes &d = c->d;
-  kh::PrepIn &pi = c->prep;
-  std::vector<Col> cols;
-  for (int r = 0; r < KOORDHIP_NRES; r++) {
-    cols.push_back({const_cast<double *>(d.alloc[r]), rows->alloc[r], 8, true, "alloc"});
-    cols.push_back({d.requested[r], rows->requested[r], 8, true, "requested"});
-  }
-  cols.push_back({const_cast<int32_t *>(d.alloc_pods), rows->alloc_pods, 4, false, "alloc_pods"});
-  cols.push_back({d.npods, rows->npods, 4, false, "npods"});
-  cols.push_back({d.nz_cpu, rows->nz_cpu_m, 8, true, "nz_cpu_m"});
-  cols.push_back({d.nz_mem, rows->nz_mem, 8, true, "nz_mem"});
-  cols.push_back({const_cast<double *>(d.la_alloc_cpu), rows->la_alloc_cpu_m, 8, true, "la_alloc_cpu_m"});
-  cols.push_back({const_cast<double *>(d.la_alloc_mem), rows->la_alloc_mem, 8, true, "la_alloc_mem"});
-  cols.push_back({d.la_used_cpu, rows->la_used_cpu_m, 8, true, "la_used_cpu_m"});
-  cols.push_back({d.la_used_mem, rows->la_used_mem, 8, true, "la_used_mem"});
-  cols.push_back({d.la_used_prod_cpu, rows->la_used_prod_cpu_m, 8, true, "la_used_prod_cpu_m"});
-  cols.push_back({d.la_used_prod_mem, rows->la_used_prod_mem, 8, true, "la_used_prod_mem"});
-  for (int r = 0; r < 2; r++) {
-    cols.push_back({const_cast<int64_t *>(pi.used_m[r]), rows->laf_used_m[r], 8, false, "laf_used_m"});
-    cols.push_back({const_cast<int64_t *>(pi.total_m[r]), rows->laf_total_m[r], 8, false, "laf_total_m"});
-    cols.push_back({const_cast<int64_t *>(pi.prod_used_m[r]), rows->laf_prod_used_m[r], 8, false, "laf_prod_used_m"});
-    cols.push_back({const_cast<int64_t *>(pi.thr[r]), rows->laf_thr[r], 8, false, "laf_thr"});
-    cols.push_back({const_cast<int64_t *>(pi.prod_thr[r]), rows->laf_prod_thr[r], 8, false, "laf_prod_thr"});
-  }
-  cols.push_back({const_cast<uint8_t *>(pi.la_flags), rows->la_flags, 1, false, "la_flags"});
-  if (numa_rows) {
-    kh::DevNuma &nu = c->d.nu;
-    cols.push_back({const_cast<int32_t *>(nu.node_cls), rows->numa_class, 4, false, "numa_class"});
-    cols.push_back({nu.cnt, rows->numa_alloc_cnt, 4, false, "numa_alloc_cnt"});
-    cols.push_back({const_cast<uint8_t *>(nu.nflags), rows->numa_flags, 1, false, "numa_flags"});
-    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) {
-      cols.push_back({nu.fr[w], rows->numa_free[w], 8, false, "numa_free"});
-      cols.push_back({nu.ep[w], rows->numa_excl_pcpu[w], 8, false, "numa_excl_pcpu"});
-      cols.push_back({nu.en[w], rows->numa_excl_numa[w], 8, false, "numa_excl_numa"});
-    }
-  }
-  if (amp_rows)
-    cols.push_back({const_cast<double *>(c->d.nu.amp), rows->numa_amp_cpu, 8, false, "numa_amp_cpu"});
-  if (c->d.sallow && rows->static_allow)
-    cols.push_back({const_cast<uint32_t *>(c->d.sallow), rows->static_allow, 4, false, "static_allow"});
-  if (resv_rows) {  // slot q of the rows -> slot q of the nodes (the same indices)
-    kh::DevResv &rv = c->d.rv;
-    const size_t dn = (size_t)rv.stride, sm = (size_t)m;
-    for (int32_t q = 0; q < rslots; q++) {
-      cols.push_back({const_cast<uint32_t *>(rv.flags) + q * dn, rows->resv_flags + q * sm, 4, false, "resv_flags"});
-      cols.push_back({const_cast<int32_t *>(rv.rank) + q * dn, rows->resv_order_rank + q * sm, 4, false, "resv_order_rank"});
-      cols.push_back({rv.rn + q * dn, rows->resv_assigned + q * sm, 4, false, "resv_assigned"});
-      for (int k = 0; k < 2; k++) {
-        cols.push_back({const_cast<double *>(rv.ra[k]) + q * dn, rows->resv_alloc[k] + q * sm, 8, true, "resv_alloc"});
-        cols.push_back({const_cast<double *>(rv.rz[k]) + q * dn, rows->resv_nz[k] + q * sm, 8, true, "resv_nz"});
-        cols.push_back({rv.rd[k] + q * dn, rows->resv_allocated[k] + q * sm, 8, true, "resv_allocated"});
-      }
-      if (rc_rows[0])
-        for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++)
-          cols.push_back({rv.rc[w] + q * dn, rc_rows[w] + q * sm, 8, false, "resv_cpus"});
-    }
-  }
-  // the device-holding reservation of every row with reservation columns (none: cleared)
-  std::vector<int32_t> no_rslot;
-  std::vector<int64_t> no_rdev, no_rx;
-  bool rows_x = false;
-  if (resv_rows && c->d.dv.rslot) {
-    kh::DevDev &dv = c->d.dv;
-    const int32_t rb = 2 * KOORDHIP_DEV_TYPES * dv.slots * KOORDHIP_DEV_RES;
-    if (!rdev_rows) {
-      no_rslot.assign((size_t)m, -1);
-      no_rdev.assign((size_t)m * rb, 0);
-    }
-    cols.push_back({const_cast<int32_t *>(dv.rslot), rdev_rows ? rows->resv_dev_slot : no_rslot.data(), 4, false,
-                    "resv_dev_slot"});
-    cols.push_back({dv.rdev, rdev_rows ? rows->resv_dev : no_rdev.data(), rb * 8, false, "resv_dev"});
-    if (dv.rxa) {
-      const bool given = rdev_rows && rows->resv_xalloc;
-      if (!given || !rows->resv_xallocated) no_rx.assign((size_t)m * KOORDHIP_NXRES, 0);
-      for (int j = 0; j < KOORDHIP_NXRES; j++) {
-        cols.push_back({const_cast<int64_t *>(dv.rxa) + (size_t)j * c->n,
-                        (given ? rows->resv_xalloc : no_rx.data()) + (size_t)j * m, 8, false, "resv_xalloc"});
-        cols.push_back({dv.rxd + (size_t)j * c->n,
-                        ((given && rows->resv_xallocated) ? rows->resv_xallocated : no_rx.data()) + (size_t)j * m, 8,
-                        false, "resv_xallocated"});
-      }
-      for (size_t a = 0; given && a < (size_t)m * KOORDHIP_NXRES && !rows_x; a++) rows_x = rows->resv_xalloc[a] != 0;
-    }
-  }
-  // ABI 9: DeviceShare device rows, extended scalars, static Scores (the
-  // sequential cycle's columns; element = a node's whole device row)
+  // ABI 9: DeviceShare device rows, extended scalars, static Scores, topology
+  // keys and counts (the sequential cycle's columns): the loaded snapshot's shapes
+  const kh::DevDev &dv = c->d.dv;
   if (c->seq_profile) {
-    kh::DevDev &dv = c->d.dv;
     if (rows->dev_slots > 0) {
       if (!dv.used || rows->dev_slots != dv.slots || !rows->dev_present || !rows->dev_minor || !rows->dev_total)
         return fail(KOORDHIP_EINVAL, "update rows: device columns must match the loaded snapshot's dev_slots");
-      const int32_t S = dv.slots;
-      for (size_t a = 0; a < (size_t)m * KOORDHIP_DEV_TYPES * S * KOORDHIP_DEV_RES; a++)
-        if (rows->dev_total[a] < 0 || rows->dev_total[a] >= (1ll << 45) ||
-            (rows->dev_used && (rows->dev_used[a] < 0 || rows->dev_used[a] >= (1ll << 45))))
-          return fail(KOORDHIP_EINVAL, "update rows: dev_total / dev_used out of [0, 2^45)");
-      for (int32_t j = 0; j < m; j++) {
-        int64_t mem = -1;
-        for (int32_t q = 0; q < S; q++) {
-          const size_t a = ((size_t)j * KOORDHIP_DEV_TYPES + KOORDHIP_DEV_GPU) * S + q;
-          const int64_t *t = rows->dev_total + a * KOORDHIP_DEV_RES;
-          if (rows->dev_minor[a] < 0 || (t[0] == 0 && t[1] == 0 && t[2] == 0)) continue;
-          if (t[2] <= 0 || (mem >= 0 && t[2] != mem)) return fail(KOORDHIP_EINVAL, "update rows: GPU memory sizes differ");
-          mem = t[2];
-        }
-      }
-      const int32_t rb = KOORDHIP_DEV_TYPES * S;
-      cols.push_back({const_cast<uint8_t *>(dv.present), rows->dev_present, 1, false, "dev_present"});
-      cols.push_back({const_cast<int32_t *>(dv.minor), rows->dev_minor, rb * 4, false, "dev_minor"});
-      cols.push_back({const_cast<int64_t *>(dv.total), rows->dev_total, rb * KOORDHIP_DEV_RES * 8, false, "dev_total"});
-      if (rows->dev_used) cols.push_back({dv.used, rows->dev_used, rb * KOORDHIP_DEV_RES * 8, false, "dev_used"});
+      if (int e = check_dev_rows(rows, m, "update rows: ")) return e;
     }
     if (rows->xalloc && !dv.xalloc) return fail(KOORDHIP_EINVAL, "extended scalars need the xalloc column at load_snapshot");
-    for (int j = 0; j < KOORDHIP_NXRES; j++) {
-      if (rows->xalloc)
-        cols.push_back({const_cast<int64_t *>(dv.xalloc) + (size_t)j * c->n, rows->xalloc + (size_t)j * m, 8, false, "xalloc"});
-      if (rows->xrequested)
-        cols.push_back({dv.xreq + (size_t)j * c->n, rows->xrequested + (size_t)j * m, 8, false, "xrequested"});
-    }
-    for (int w = 0; w < 2; w++) {
-      if (!rows->static_score[w]) continue;
-      if (!dv.sscore[w]) return fail(KOORDHIP_EINVAL, "static scores need their column at load_snapshot");
-      for (int q = 0; q < KOORDHIP_MAX_STATIC_CLASSES; q++)
-        cols.push_back({const_cast<uint16_t *>(dv.sscore[w]) + (size_t)q * c->n, rows->static_score[w] + (size_t)q * m, 2,
-                        false, "static_score"});
-    }
-    // PodTopologySpread rows: the same keys / constraint table as the loaded snapshot
+    for (int w = 0; w < 2; w++)
+      if (rows->static_score[w] && !dv.sscore[w])
+        return fail(KOORDHIP_EINVAL, "static scores need their column at load_snapshot");
     if (rows->pts_keys > 0) {
       const kh::PtsArgs &pa = c->pts;
       if (!pa.dom || rows->pts_keys != pa.keys || rows->pts_cons != pa.cons || !rows->pts_dom || !rows->pts_elig ||
           (pa.cons > 0 && !rows->pts_cnt))
         return fail(KOORDHIP_EINVAL, "update rows: PodTopologySpread columns must match the loaded snapshot's tables");
-      for (int k = 0; k < pa.keys; k++) {
-        for (int32_t j = 0; j < m; j++) {
-          const int32_t v = rows->pts_dom[(size_t)k * m + j];
-          if (v < -1 || v >= (((pa.host >> k) & 1u) ? c->n : KOORDHIP_PTS_DOMAINS) ||
-              (((pa.host >> k) & 1u) && v >= 0 && v != idx[j]))
-            return fail(KOORDHIP_EINVAL, "update rows: pts_dom out of range");
-        }
-        cols.push_back({const_cast<int32_t *>(pa.dom) + (size_t)k * c->n, rows->pts_dom + (size_t)k * m, 4, false,
-                        "pts_dom"});
-      }
-      for (int cc = 0; cc < pa.cons; cc++)
-        cols.push_back({pa.cnt + (size_t)cc * c->n, rows->pts_cnt + (size_t)cc * m, 4, false, "pts_cnt"});
-      cols.push_back({const_cast<uint16_t *>(pa.elig), rows->pts_elig, 2, false, "pts_elig"});
+      if (int e = check_pts_dom(rows->pts_dom, pa.keys, m, pa.host, c->n, nullptr, idx, "update rows: ")) return e;
     }
-    // InterPodAffinity rows: the loaded snapshot's entries
-    if (rows->ipa_ents > 0) {
-      const kh::IpaArgs &ia = c->ipa;
-      if (!ia.cnt || rows->ipa_ents != ia.ents || !rows->ipa_cnt)
-        return fail(KOORDHIP_EINVAL, "update rows: InterPodAffinity columns must match the loaded snapshot's entries");
-      for (int q = 0; q < ia.ents; q++)
-        cols.push_back({ia.cnt + (size_t)q * c->n, rows->ipa_cnt + (size_t)q * m, 4, false, "ipa_cnt"});
-    }
+    if (rows->ipa_ents > 0 && (!c->ipa.cnt || rows->ipa_ents != c->ipa.ents || !rows->ipa_cnt))
+      return fail(KOORDHIP_EINVAL, "update rows: InterPodAffinity columns must match the loaded snapshot's entries");
   } else if (rows->dev_slots > 0 || rows->xalloc || rows->static_score[0] || rows->static_score[1] ||
              rows->pts_keys > 0 || rows->ipa_ents > 0) {
     return fail(KOORDHIP_EINVAL, "device / extended-scalar / static-score rows need DeviceShare or a normalized Score "
                                  "plugin in the profile");
   }
-  if (zrows) {  // [m][2][ZMAX] f64 rows, scattered as one ZoneRow element per row
-    kh::DevNuma &nu = c->d.nu;
-    cols.push_back({const_cast<double *>(nu.za), zrow_a.data(), (int32_t)sizeof(kh::ZoneRow), false, "numa_zone_alloc"});
-    cols.push_back({nu.zu, zrow_u.data(), (int32_t)sizeof(kh::ZoneRow), false, "numa_zone_used"});
+  // ---- the rows as the loaded columns take them.  A NULL source leaves its
+  //      column alone, so the families these rows do not carry are dropped
+  //      here (a column the snapshot was loaded without has no record to
+  //      begin with) ...
+  koordhip_node_soa take = *rows;
+  if (!numa_rows) {
+    take.numa_class = take.numa_alloc_cnt = nullptr;
+    take.numa_flags = nullptr;
+    take.numa_amp_cpu = nullptr;
+    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) take.numa_free[w] = take.numa_excl_pcpu[w] = take.numa_excl_numa[w] = nullptr;
   }
-  const size_t seg_idx = ((size_t)m * 4 + 7) & ~(size_t)7;
-  size_t bytes = seg_idx;
-  std::vector<size_t> off(cols.size());
-  for (size_t q = 0; q < cols.size(); q++) {
-    off[q] = bytes;
-    bytes += ((size_t)m * cols[q].esize + 7) & ~(size_t)7;
+  // (zone rows go as converted above, [m] ZoneRow elements of f64)
+  take.numa_zone_alloc = zrows ? reinterpret_cast<const int64_t *>(zrow_a.data()) : nullptr;
+  take.numa_zone_used = zrows ? reinterpret_cast<const int64_t *>(zrow_u.data()) : nullptr;
+  if (rows->dev_slots <= 0) {
+    take.dev_present = nullptr;
+    take.dev_minor = nullptr;
+    take.dev_total = take.dev_used = nullptr;
   }
-  std::vector<uint8_t> &img = c->upd_host;
-  img.assign(bytes, 0);
-  std::memcpy(img.data(), idx, (size_t)m * 4);
-  for (size_t q = 0; q < cols.size(); q++) {
-    const Col &k = cols[q];
-    if (k.q) {
-      const int64_t *src = static_cast<const int64_t *>(k.src);
-      double *o = reinterpret_cast<double *>(img.data() + off[q]);
-      for (int32_t j = 0; j < m; j++) {
-        if (!exact_ok(src[j]))
-          return fail(KOORDHIP_EINVAL, std::string(k.what) + ": quantity outside [0, 2^45), the engine's exact range");
-        o[j] = (double)src[j];
+  if (rows->pts_keys <= 0) {
+    take.pts_dom = nullptr;
+    take.pts_elig = nullptr;
+  }
+  if (rows->pts_keys <= 0 || c->pts.cons == 0) take.pts_cnt = nullptr;
+  if (rows->ipa_ents <= 0) take.ipa_cnt = nullptr;
+  // ... except that rows carrying the reservation columns replace ALL of the
+  // node's reservation state: what they do not bring is cleared -- no reserved
+  // CPUs, no device-holding reservation (slot -1, zero devices, zero scalars:
+  // a different reservation moving into the slot cannot inherit them)
+  std::vector<uint64_t> no_rc;
+  std::vector<int32_t> no_rslot;
+  std::vector<int64_t> no_rdev, no_rx;
+  bool rows_x = false;
+  if (!resv_rows) {
+    take.resv_flags = nullptr;
+    take.resv_order_rank = take.resv_assigned = take.resv_dev_slot = nullptr;
+    take.resv_dev = take.resv_xalloc = take.resv_xallocated = nullptr;
+    for (int k = 0; k < 2; k++) take.resv_alloc[k] = take.resv_nz[k] = take.resv_allocated[k] = nullptr;
+    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) take.resv_cpus[w] = nullptr;
+  } else {
+    if (c->dc.resv_cpus && !rc_rows) {
+      no_rc.assign((size_t)rslots * (size_t)m, 0ull);
+      for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) take.resv_cpus[w] = no_rc.data();
+    }
+    if (dv.rslot && !rdev_rows) {
+      no_rslot.assign((size_t)m, -1);
+      no_rdev.assign((size_t)m * 2 * KOORDHIP_DEV_TYPES * dv.slots * KOORDHIP_DEV_RES, 0);
+      take.resv_dev_slot = no_rslot.data();
+      take.resv_dev = no_rdev.data();
+    }
+    if (dv.rxa) {
+      const bool given = rdev_rows && rows->resv_xalloc;
+      if (!given || !rows->resv_xallocated) {
+        no_rx.assign((size_t)m * KOORDHIP_NXRES, 0);
+        take.resv_xallocated = no_rx.data();
+        if (!given) take.resv_xalloc = no_rx.data();
       }
-    } else {
-      std::memcpy(img.data() + off[q], k.src, (size_t)m * k.esize);
+      for (size_t a = 0; given && a < (size_t)m * KOORDHIP_NXRES && !rows_x; a++) rows_x = rows->resv_xalloc[a] != 0;
     }
   }
+  // ---- one host staging image: [idx][segment 0][segment 1]..., a segment per
+  //      column plane
+  const std::vector<kh::RowSeg> segs = kh::row_segments(c->cols, &take, m, c->n);
+  std::vector<size_t> off;
+  std::string bad;
+  if (!kh::pack_rows(segs, idx, m, c->upd_host, off, &bad)) return fail(KOORDHIP_EINVAL, bad);
+  const size_t bytes = c->upd_host.size();
   bool alias = c->dc.la_alias;
   for (int32_t j = 0; j < m && alias; j++)
     if (rows->la_alloc_cpu_m[j] != rows->alloc[KOORDHIP_RES_CPU][j] || rows->la_alloc_mem[j] != rows->alloc[KOORDHIP_RES_MEM][j])
@@ -1765,12 +1550,12 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
   if (int e = ensure(c, &c->d_upd, &c->upd_cap, bytes)) return e;
   uint8_t *dev = static_cast<uint8_t *>(c->d_upd);
   const int32_t *d_idx = reinterpret_cast<const int32_t *>(dev);
-  HIP_TRY(hipMemcpyAsync(dev, img.data(), bytes, hipMemcpyHostToDevice, c->stream));
-  for (size_t q = 0; q < cols.size(); q++) {
-    const Col &k = cols[q];
+  HIP_TRY(hipMemcpyAsync(dev, c->upd_host.data(), bytes, hipMemcpyHostToDevice, c->stream));
+  for (size_t q = 0; q < segs.size(); q++) {
+    const kh::RowSeg &k = segs[q];
     const void *src = dev + off[q];
     if (k.esize > 8)  // whole rows (NUMA zone rows, device rows)
-      HIP_TRY(kh::launch_scatter_rows(k.dst, src, d_idx, m, k.esize, c->stream));
+      HIP_TRY(kh::launch_scatter_rows(k.dst, src, d_idx, m, (int32_t)k.esize, c->stream));
     else if (k.esize == 2)
       HIP_TRY(kh::launch_scatter<uint16_t>(static_cast<uint16_t *>(k.dst), static_cast<const uint16_t *>(src), d_idx, m,
                                            c->stream));
@@ -1790,7 +1575,7 @@ int koordhip_update_nodes(koordhip_ctx *c, const int32_t *idx, const koordhip_no
     c->seq = true;
   }
   if (amp_any) c->dc.amp = 1;
-  HIP_TRY(kh::launch_prep_flags(pi, d, d_idx, m, c->stream));
+  HIP_TRY(kh::launch_prep_flags(c->prep, c->d, d_idx, m, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));  // the host image may be reused by the next call
   return 0;
 }
@@ -1904,8 +1689,7 @@ int koordhip_read_resv_devices(koordhip_ctx *c, int64_t *resv_dev) {
   }
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  HIP_TRY(hipMemcpy(resv_dev, c->d.dv.rdev, nd * sizeof(int64_t), hipMemcpyDeviceToHost));
-  return 0;
+  return download(c, c->d.dv.rdev, resv_dev);
 }
 
 int koordhip_read_resv_scalars(koordhip_ctx *c, int64_t *resv_xallocated) {
@@ -1918,8 +1702,7 @@ int koordhip_read_resv_scalars(koordhip_ctx *c, int64_t *resv_xallocated) {
     std::memset(resv_xallocated, 0, nx * sizeof(int64_t));
     return 0;
   }
-  HIP_TRY(hipMemcpy(resv_xallocated, c->d.dv.rxd, nx * sizeof(int64_t), hipMemcpyDeviceToHost));
-  return 0;
+  return download(c, c->d.dv.rxd, resv_xallocated);
 }
 
 static int check_reserve_pods(const koordhip_ctx *c, const koordhip_pod *pods, int32_t n, bool *any);
@@ -2287,7 +2070,7 @@ int koordhip_read_devices(koordhip_ctx *c, int64_t *dev_used, int64_t *xrequeste
   const size_t nd = (size_t)c->n * KOORDHIP_DEV_TYPES * c->d.dv.slots * KOORDHIP_DEV_RES;
   if (dev_used && nd) {
     if (c->d.dv.used) {
-      HIP_TRY(hipMemcpy(dev_used, c->d.dv.used, nd * sizeof(int64_t), hipMemcpyDeviceToHost));
+      if (int e = download(c, c->d.dv.used, dev_used)) return e;
     } else {
       std::memset(dev_used, 0, nd * sizeof(int64_t));
     }
@@ -2295,7 +2078,7 @@ int koordhip_read_devices(koordhip_ctx *c, int64_t *dev_used, int64_t *xrequeste
   const size_t nx = (size_t)c->n * KOORDHIP_NXRES;
   if (xrequested) {
     if (c->d.dv.xreq) {
-      HIP_TRY(hipMemcpy(xrequested, c->d.dv.xreq, nx * sizeof(int64_t), hipMemcpyDeviceToHost));
+      if (int e = download(c, c->d.dv.xreq, xrequested)) return e;
     } else {
       std::memset(xrequested, 0, nx * sizeof(int64_t));
     }
@@ -2308,10 +2091,8 @@ int koordhip_read_ipa(koordhip_ctx *c, int32_t *cnt) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const size_t nb = (size_t)c->n * std::max(0, c->ipa.ents) * sizeof(int32_t);
-  if (!c->ipa.cnt || !nb) return 0;
-  HIP_TRY(hipMemcpy(cnt, c->ipa.cnt, nb, hipMemcpyDeviceToHost));
-  return 0;
+  if (!c->ipa.cnt) return 0;
+  return download(c, c->ipa.cnt, cnt);
 }
 
 int koordhip_read_pts(koordhip_ctx *c, int32_t *cnt) {
@@ -3465,60 +3246,18 @@ int koordhip_place_stream(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_p
   return koordhip_fetch_placements(c, out_node, n_pods);
 }
 
-// mutable columns: (device pointer, bytes)
-static std::vector<std::pair<void *, size_t>> mutable_cols(koordhip_ctx *c) {
-  const size_t n = c->n, b = n * sizeof(int64_t);
-  std::vector<std::pair<void *, size_t>> v;
-  for (int r = 0; r < KOORDHIP_NRES; r++) v.push_back({c->d.requested[r], b});
-  v.push_back({c->d.nz_cpu, b});
-  v.push_back({c->d.nz_mem, b});
-  v.push_back({c->d.npods, n * sizeof(int32_t)});
-  v.push_back({c->d.la_used_cpu, b});
-  v.push_back({c->d.la_used_mem, b});
-  v.push_back({c->d.la_used_prod_cpu, b});
-  v.push_back({c->d.la_used_prod_mem, b});
-  v.push_back({c->d.flags, n});
-  if (c->numa) {
-    const kh::DevNuma &nu = c->d.nu;
-    for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) {
-      v.push_back({nu.fr[w], n * sizeof(uint64_t)});
-      v.push_back({nu.ep[w], n * sizeof(uint64_t)});
-      v.push_back({nu.en[w], n * sizeof(uint64_t)});
-    }
-    v.push_back({nu.cnt, n * sizeof(int32_t)});
-    if (nu.zu) v.push_back({nu.zu, n * 2 * KOORDHIP_NUMA_MAX_ZONES * sizeof(double)});
-  }
-  if (c->d.dv.used)
-    v.push_back({c->d.dv.used, n * KOORDHIP_DEV_TYPES * (size_t)c->d.dv.slots * KOORDHIP_DEV_RES * sizeof(int64_t)});
-  if (c->d.dv.xreq) v.push_back({c->d.dv.xreq, n * KOORDHIP_NXRES * sizeof(int64_t)});
-  if (c->d.dv.rxd) v.push_back({c->d.dv.rxd, n * KOORDHIP_NXRES * sizeof(int64_t)});
-  if (c->d.dv.rdev)
-    v.push_back({c->d.dv.rdev, n * 2 * KOORDHIP_DEV_TYPES * (size_t)c->d.dv.slots * KOORDHIP_DEV_RES * sizeof(int64_t)});
-  if (c->pts.cnt) v.push_back({c->pts.cnt, n * (size_t)std::max(1, c->pts.cons) * sizeof(int32_t)});
-  if (c->ipa.cnt) v.push_back({c->ipa.cnt, n * (size_t)c->ipa.ents * sizeof(int32_t)});
-  if (c->dc.resv) {
-    const size_t sl = (size_t)c->d.rv.slots;
-    v.push_back({c->d.rv.rd[0], b * sl});
-    v.push_back({c->d.rv.rd[1], b * sl});
-    v.push_back({c->d.rv.rn, n * sl * sizeof(int32_t)});
-    if (c->dc.resv_cpus)
-      for (int w = 0; w < KOORDHIP_NUMA_WORDS; w++) v.push_back({c->d.rv.rc[w], n * sl * sizeof(uint64_t)});
-  }
-  return v;
-}
-
+// A checkpoint is a copy of every column a Reserve mutates (kh::Column::mut),
+// kept beside the column and released with it.
 int koordhip_checkpoint(koordhip_ctx *c) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   HIP_TRY(hipSetDevice(c->device));
-  auto cols = mutable_cols(c);
-  if (c->ckpt.size() != cols.size()) {
-    for (void *p : c->ckpt) (void)hipFree(p);
-    c->ckpt.assign(cols.size(), nullptr);
-    for (size_t i = 0; i < cols.size(); i++) HIP_TRY(hipMalloc(&c->ckpt[i], std::max<size_t>(cols[i].second, 1)));
+  for (kh::Column &k : c->cols) {
+    if (!k.mut) continue;
+    const size_t bytes = k.bytes(c->n);
+    if (!k.ckpt) HIP_TRY(hipMalloc(&k.ckpt, std::max<size_t>(bytes, 1)));
+    if (bytes) HIP_TRY(hipMemcpyAsync(k.ckpt, k.dev, bytes, hipMemcpyDeviceToDevice, c->stream));
   }
-  for (size_t i = 0; i < cols.size(); i++)
-    if (cols[i].second) HIP_TRY(hipMemcpyAsync(c->ckpt[i], cols[i].first, cols[i].second, hipMemcpyDeviceToDevice, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -3526,12 +3265,12 @@ int koordhip_checkpoint(koordhip_ctx *c) {
 int koordhip_restore(koordhip_ctx *c) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
-  auto cols = mutable_cols(c);
-  if (c->ckpt.size() != cols.size()) return fail(KOORDHIP_ESTATE, "no checkpoint");
+  for (const kh::Column &k : c->cols)
+    if (k.mut && !k.ckpt) return fail(KOORDHIP_ESTATE, "no checkpoint");
   HIP_TRY(hipSetDevice(c->device));
   c->diag_valid = false;
-  for (size_t i = 0; i < cols.size(); i++)
-    if (cols[i].second) HIP_TRY(hipMemcpyAsync(cols[i].first, c->ckpt[i], cols[i].second, hipMemcpyDeviceToDevice, c->stream));
+  for (const kh::Column &k : c->cols)
+    if (k.mut && k.bytes(c->n)) HIP_TRY(hipMemcpyAsync(k.dev, k.ckpt, k.bytes(c->n), hipMemcpyDeviceToDevice, c->stream));
   return 0;
 }
 
