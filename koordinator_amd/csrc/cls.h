@@ -22,7 +22,7 @@ struct ClsMeta {
 static_assert(sizeof(ClsMeta) == 16, "ClsMeta");
 
 constexpr int32_t kClsCap = 4096;   // keys a buffer holds (a build fills kClsTarget, log insertions the rest)
-constexpr int32_t kClsTarget = 2048;  // keys a build takes (the best ones, ties by lowest index)
+// (kClsTarget, the keys a build takes, and kClsLdsBudget: place_plan.hpp, through kernels.h)
 constexpr int32_t kClsBuildRows = 64;  // class rows one build launch evaluates
 
 // Device words of the class pipeline: the round pipeline's flags, and per

@@ -670,14 +670,14 @@ hipError_t launch_cls_run(const DevCfg &c, const DevNodes &d, const DevPod *cls_
                           hipStream_t s) {
   if (n_cls <= 0) return hipSuccess;
   const size_t lds = cls_run_lds(d.n, monotone);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
+  if (lds > kClsLdsBudget) return hipErrorInvalidValue;
   const int nm = side_mode(c);
 #define KH_CLS(NN)                                                                                                   \
   do {                                                                                                               \
     static bool attr = false;                                                                                        \
     if (!attr) {                                                                                                     \
       if (hipError_t e = hipFuncSetAttribute((const void *)k_cls_run<NN>,                                            \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))                \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)kClsLdsBudget)) \
         return e;                                                                                                    \
       attr = true;                                                                                                   \
     }                                                                                                                \

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "eval.hpp"
+#include "place_plan.hpp"  // kResolveMaxK: the longest list the resolve takes (RES_MAXP)
 
 namespace kh {
 
@@ -81,7 +82,6 @@ hipError_t launch_scatter_rows(void *dst, const void *src, const int32_t *idx, i
 // `sync`; M' is handed between launches in mbuf ({count, nodes}, lag 1).  The
 // evaluation stream(s) bracket each round with k_wait_resolved (before k_scan)
 // and k_signal_lists (after the lists).
-constexpr int32_t kResolveMaxK = 128;  // longest list the resolve takes (RES_MAXP)
 // nm: the kernels' node-row mode, 0 none, 1 NodeNUMAResource, 2 + topology-policy zones, 3 + Reservation
 int side_mode(const DevCfg &c);
 // the last evaluation / resolve kernel instantiation launched by this host
