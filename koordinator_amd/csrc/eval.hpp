@@ -42,6 +42,32 @@ __device__ __forceinline__ void st_wt(T *p, T v) {
   }
 }
 
+// The node columns are HBM buffers.  A column pointer that the compiler cannot
+// trace back to a kernel argument (k_resolve reads them from its LDS pointer
+// table) is a generic pointer to it: every access through it would be a
+// flat_ instruction, which also counts in lgkmcnt and so ties the row traffic
+// to the LDS bookkeeping around it.  The row helpers below (load_row,
+// store_row_wt, the side rows) go through as_global / st_wt_g: global_load /
+// global_store ... sc1 whatever the pointer's origin.  Where the pointer is a
+// kernel argument the compiler knew as much already.
+template <typename T>
+using gptr = __attribute__((address_space(1))) T *;
+template <typename T>
+__device__ __forceinline__ gptr<T> as_global(T *p) {
+  return (gptr<T>)p;
+}
+// st_wt on a pointer known to be HBM (same sc1 write-through agent-scope store)
+template <typename T>
+__device__ __forceinline__ void st_wt_g(T *p, T v) {
+  if constexpr (sizeof(T) == 8) {
+    __hip_atomic_store((gptr<uint64_t>)p, __builtin_bit_cast(uint64_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else if constexpr (sizeof(T) == 4) {
+    __hip_atomic_store((gptr<uint32_t>)p, __builtin_bit_cast(uint32_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  } else {
+    __hip_atomic_store((gptr<uint8_t>)p, __builtin_bit_cast(uint8_t, v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // device-side node flag bits (flags column, maintained on device)
 enum : uint32_t {
   NF_LA_OK_NONPROD = 1u,  // LoadAware Filter passes for non-prod pods
@@ -237,7 +263,7 @@ __device__ __forceinline__ Need need_all(const DevCfg &c) {
 
 // NodeNUMAResource columns of node i.
 __device__ __forceinline__ void load_zones(NumaRow &r, const DevNodes &d, int32_t i) {
-  const double *zu = d.nu.zu + (size_t)i * 2 * ZMAX;
+  const gptr<const double> zu = as_global<const double>(d.nu.zu) + (size_t)i * 2 * ZMAX;
   r.za = d.nu.za + (size_t)i * 2 * ZMAX;  // static: read in place by the zone code
 #pragma unroll
   for (int q = 0; q < ZMAX; q++) {
@@ -679,36 +705,36 @@ __device__ __forceinline__ void apply_delta(NV &v, const DevPod &p, int sign) {
 __device__ __forceinline__ void load_row(NV &v, const DevNodes &d, int32_t i) {
 #pragma unroll
   for (int r = 0; r < KOORDHIP_NRES; r++) {
-    v.a[r] = d.alloc[r][i];
-    v.r[r] = d.requested[r][i];
+    v.a[r] = as_global(d.alloc[r])[i];
+    v.r[r] = as_global(d.requested[r])[i];
   }
-  v.a_pods = d.alloc_pods[i];
-  v.npods = d.npods[i];
-  v.nz_cpu = d.nz_cpu[i];
-  v.nz_mem = d.nz_mem[i];
-  v.la_a_cpu = d.la_alloc_cpu[i];
-  v.la_a_mem = d.la_alloc_mem[i];
-  v.la_u_cpu = d.la_used_cpu[i];
-  v.la_u_mem = d.la_used_mem[i];
-  v.la_up_cpu = d.la_used_prod_cpu[i];
-  v.la_up_mem = d.la_used_prod_mem[i];
-  v.flags = d.flags[i];
-  v.sa = d.sallow ? d.sallow[i] : 0xFFFFFFFFu;
+  v.a_pods = as_global(d.alloc_pods)[i];
+  v.npods = as_global(d.npods)[i];
+  v.nz_cpu = as_global(d.nz_cpu)[i];
+  v.nz_mem = as_global(d.nz_mem)[i];
+  v.la_a_cpu = as_global(d.la_alloc_cpu)[i];
+  v.la_a_mem = as_global(d.la_alloc_mem)[i];
+  v.la_u_cpu = as_global(d.la_used_cpu)[i];
+  v.la_u_mem = as_global(d.la_used_mem)[i];
+  v.la_up_cpu = as_global(d.la_used_prod_cpu)[i];
+  v.la_up_mem = as_global(d.la_used_prod_mem)[i];
+  v.flags = as_global(d.flags)[i];
+  v.sa = d.sallow ? as_global(d.sallow)[i] : 0xFFFFFFFFu;
 }
 
 template <bool Z = true>
 __device__ __forceinline__ void load_numa_row(NumaRow &r, const DevNodes &d, int32_t i) {
-  r.cls = d.nu.node_cls[i];
-  r.nflags = d.nu.nflags[i];
-  r.cnt = d.nu.cnt[i];
+  r.cls = as_global(d.nu.node_cls)[i];
+  r.nflags = as_global(d.nu.nflags)[i];
+  r.cnt = as_global(d.nu.cnt)[i];
 #pragma unroll
   for (int w = 0; w < NW; w++) {
-    r.fr[w] = d.nu.fr[w][i];
-    r.ep[w] = d.nu.ep[w][i];
-    r.en[w] = d.nu.en[w][i];
+    r.fr[w] = as_global(d.nu.fr[w])[i];
+    r.ep[w] = as_global(d.nu.ep[w])[i];
+    r.en[w] = as_global(d.nu.en[w])[i];
   }
   if (Z && d.nu.za && topo_policy(r.nflags) != 0) load_zones(r, d, i);
-  r.amp = d.nu.amp ? d.nu.amp[i] : 1.0;
+  r.amp = d.nu.amp ? as_global(d.nu.amp)[i] : 1.0;
 }
 
 template <bool Z = true>
@@ -771,32 +797,32 @@ __device__ __forceinline__ void store_row(const NV &v, const DevNodes &d, int32_
 // The resolve's write-back of a committed row (the mutable columns), write-through.
 __device__ __forceinline__ void store_row_wt(const NV &v, const DevNodes &d, int32_t i) {
 #pragma unroll
-  for (int r = 0; r < KOORDHIP_NRES; r++) st_wt(&d.requested[r][i], v.r[r]);
-  st_wt(&d.npods[i], v.npods);
-  st_wt(&d.nz_cpu[i], v.nz_cpu);
-  st_wt(&d.nz_mem[i], v.nz_mem);
-  st_wt(&d.la_used_cpu[i], v.la_u_cpu);
-  st_wt(&d.la_used_mem[i], v.la_u_mem);
-  st_wt(&d.la_used_prod_cpu[i], v.la_up_cpu);
-  st_wt(&d.la_used_prod_mem[i], v.la_up_mem);
-  st_wt(&d.flags[i], (uint8_t)v.flags);
+  for (int r = 0; r < KOORDHIP_NRES; r++) st_wt_g(&d.requested[r][i], v.r[r]);
+  st_wt_g(&d.npods[i], v.npods);
+  st_wt_g(&d.nz_cpu[i], v.nz_cpu);
+  st_wt_g(&d.nz_mem[i], v.nz_mem);
+  st_wt_g(&d.la_used_cpu[i], v.la_u_cpu);
+  st_wt_g(&d.la_used_mem[i], v.la_u_mem);
+  st_wt_g(&d.la_used_prod_cpu[i], v.la_up_cpu);
+  st_wt_g(&d.la_used_prod_mem[i], v.la_up_mem);
+  st_wt_g(&d.flags[i], (uint8_t)v.flags);
 }
 
 template <bool Z = true>
 __device__ __forceinline__ void store_numa_row_wt(const NumaRow &r, const DevNodes &d, int32_t i) {
-  st_wt(&d.nu.cnt[i], r.cnt);
+  st_wt_g(&d.nu.cnt[i], r.cnt);
 #pragma unroll
   for (int w = 0; w < NW; w++) {
-    st_wt(&d.nu.fr[w][i], r.fr[w]);
-    st_wt(&d.nu.ep[w][i], r.ep[w]);
-    st_wt(&d.nu.en[w][i], r.en[w]);
+    st_wt_g(&d.nu.fr[w][i], r.fr[w]);
+    st_wt_g(&d.nu.ep[w][i], r.ep[w]);
+    st_wt_g(&d.nu.en[w][i], r.en[w]);
   }
   if (Z && d.nu.za && topo_policy(r.nflags) != 0) {
     double *zu = d.nu.zu + (size_t)i * 2 * ZMAX;
 #pragma unroll
     for (int q = 0; q < ZMAX; q++) {
-      st_wt(&zu[q], r.zu[0][q]);
-      st_wt(&zu[ZMAX + q], r.zu[1][q]);
+      st_wt_g(&zu[q], r.zu[0][q]);
+      st_wt_g(&zu[ZMAX + q], r.zu[1][q]);
     }
   }
 }

@@ -1762,9 +1762,21 @@ struct ResLds {  // byte offsets into the dynamic LDS of k_resolve
   // second copies of the per-round inputs, filled by waves 1.. while wave 0
   // resolves the previous round (overlap = 0: every round loads serially)
   int32_t overlap, lists2, pods2, pre_rows2, pre_numa2, pre_node2;
+  int32_t ptab;  // the column-pointer table (res_ptab_bytes), -1: none
 };
 
 __host__ __device__ inline int32_t res_align(int32_t x) { return (x + 15) & ~15; }
+
+// The column-pointer table of k_resolve: the leading part of DevNodes that its
+// row I/O reads (load_row / store_row_wt: the 22 column pointers up to `nu`;
+// with NodeNUMAResource the side rows' DevNuma too), copied to LDS once per
+// launch.  nrow: bytes of a side row.  The Reservation builds have none: their
+// rounds are sized to the last byte of the LDS (200k nodes: 15 pods per round
+// with no byte to spare), and a table would shorten them.
+__host__ __device__ inline int32_t res_ptab_bytes(int32_t nrow) {
+  if (nrow == 0) return res_align((int32_t)offsetof(DevNodes, nu));
+  return nrow == (int32_t)sizeof(NumaRow) ? res_align((int32_t)offsetof(DevNodes, rv)) : 0;
+}
 
 // chain: room for the chained decisions' dependency masks (the plain and NUMA
 // builds; the Reservation builds are never monotone, and their rows need the LDS)
@@ -1838,6 +1850,8 @@ __host__ __device__ inline ResLds res_lds(int32_t n_pods_max, int32_t kp, int32_
   at += numa ? NUMA_LDS_CLASSES * (int32_t)sizeof(DevNumaClass) : 0;
   o.modmap = at;  // X bitmap
   at += bitmap;
+  o.ptab = res_ptab_bytes(nrow) ? at : -1;
+  at += res_ptab_bytes(nrow);
   o.overlap = overlap ? 1 : 0;
   o.lists2 = o.pods2 = o.pre_rows2 = o.pre_numa2 = o.pre_node2 = 0;
   if (overlap) {
@@ -1954,14 +1968,34 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   const int t = threadIdx.x, lane = lane_id();
   const int32_t words = (n_nodes + 31) >> 5;
   const int32_t HP = max(1, RES_PRE / P);  // prefetched list heads per pod
-  // The column pointers are read from a device-side copy of DevNodes at each
-  // (rare) row load/store instead of living in SGPRs for the whole kernel:
-  // ~40 pointers would otherwise spill through VGPR lanes in the hot loop.
-  auto nodes = [dn]() -> DevNodes {
-    const DevNodes *p = dn;
-    asm volatile("" : "+s"(p));
-    return *p;
+  // nodes(): the DevNodes a row load / store takes its column pointers from.
+  // They cannot live in SGPRs for the whole kernel (~40 pointers would spill
+  // through VGPR lanes in the hot loop), so each site re-reads the ones it
+  // needs.  Plain and NodeNUMAResource builds read them from the LDS table
+  // (ofs.ptab, filled below from the device-side DevNodes `dn`): every lane
+  // reads the same address, a broadcast ds_read, and the columns follow as
+  // global_load / global_store ... sc1 (eval.hpp as_global).  Reading `dn`
+  // itself at each site, as this kernel did, compiled to flat_load_dwordx4 of
+  // the descriptor through a VGPR address (the asm below hides the pointer's
+  // origin), an s_waitcnt vmcnt(0) lgkmcnt(0), and only then the columns, as
+  // flat_ accesses because their pointers came from memory: two dependent HBM
+  // round trips per row, once per round in wave 0's write-back.  The
+  // Reservation builds still pay the descriptor trip (no LDS to spare for a
+  // table, res_ptab_bytes); their columns are global_ accesses too.
+  auto nodes = [&]() -> decltype(auto) {
+    if constexpr (NM <= 2) {
+      return *reinterpret_cast<const DevNodes *>(lds + ofs.ptab);  // valid up to `rv` (`nu` without NUMA)
+    } else {
+      const DevNodes *p = dn;
+      asm volatile("" : "+s"(p));
+      return DevNodes(*p);
+    }
   };
+  if constexpr (NM <= 2) {
+    constexpr int PW = (int)((NUMA ? offsetof(DevNodes, rv) : offsetof(DevNodes, nu)) / 8);
+    static_assert(PW <= RES_THREADS, "one 8-byte word of the pointer table per thread");
+    if (t < PW) reinterpret_cast<uint64_t *>(lds + ofs.ptab)[t] = reinterpret_cast<const uint64_t *>(dn)[t];
+  }
   const bool two = kp > 64;
   const bool chain_on = (monotone & 2) && ofs.dep >= 0;  // the chained decisions (phase 2c)
   const uint64_t t_kernel = (dbg && t == 0) ? stamp() : 0;
@@ -1983,7 +2017,7 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   }
   const DevNumaClass *cls = ncls;
   if constexpr (NUMA) {  // topology classes -> LDS
-    const int32_t nc = nodes().nu.ncls;
+    const int32_t nc = dn->nu.ncls;  // (the pointer table is not filled yet)
     if (nc <= NUMA_LDS_CLASSES) {
       uint4 *dst = reinterpret_cast<uint4 *>(lds + ofs.classes);
       const uint4 *src = reinterpret_cast<const uint4 *>(ncls);
@@ -2035,29 +2069,34 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   uint64_t c_ext = 0, n_ext = 0;                     // device pods: cycles from the hand-off to the worker's answer, pods
   // ---- a round's global reads: lists -> LDS (stride kp, zero padded), pod
   //      records, and the rows of each pod's first HP list entries (slot HP j + q)
-  // Every loop keeps several global loads in flight per thread before its LDS
-  // stores: wave 1 alone runs this for the next round (64 threads), where one
-  // load-store pair per iteration serialised ~40 HBM round trips.
+  // Two dependent HBM round trips (wave 1..3 run this for the next round, and
+  // wave 0 waits at the end-of-round barrier for whatever they still owe):
+  //   A. the thread's list-head entries, its first batch of list vectors (16-B
+  //      vectors of the dense [rn][k] global lists) and its pod-record vectors,
+  //      all issued before the first wait.  None depends on another: an index
+  //      past the end is clamped (the value is loaded and dropped), and a batch
+  //      slot no thread needs is skipped by a wave-uniform test.
+  //   B. the head rows' columns, which need only the nodes of the head
+  //      entries; A's LDS stores sit between B's issue and its wait.
+  // Lists longer than one batch (one loader wave, or a large P x k) stream
+  // through a loop that issues batch i + 1 before batch i's stores wait.
   auto load_round = [&](int32_t rr, int32_t rp0, int32_t rn, uint64_t *Lk, DevPod *Lp, NV *Pr, NR *Pn,
                         int32_t *Pnode, int32_t tid, int32_t nth) {
-    // Issue order keeps the HBM round trips few for wave 1 alone (one
-    // load-store pair per iteration serialised ~40 of them): the list-head
-    // entries with the first batch of list loads (16-B vectors of the dense
-    // [rn][k] global lists), then the head rows' column loads while the
-    // remaining list batches stream in.
     const uint64_t *L = lists0 + (size_t)(rr & (2 * lag - 1)) * list_buf;
-    const int32_t tot = rn * k;
-    int32_t nd[2];
+    const int32_t tot = rn * k;  // >= 1: a round has a pod, a list an entry
+    // ---- trip A
+    uint64_t he[2] = {0, 0};
+    bool hv[2];
 #pragma unroll
     for (int u = 0; u < 2; u++) {
       const int32_t sl = tid + u * nth, j = sl / HP, q = sl - j * HP;
-      nd[u] = -1;
-      if (sl < RES_PRE && j < rn && q < k) {
-        const uint64_t e = L[(size_t)j * k + q];
-        if (e != 0) nd[u] = key_node(e);
-      }
+      hv[u] = sl < RES_PRE && j < rn && q < k;
+      if (u * nth < RES_PRE) he[u] = L[min(j * k + q, tot - 1)];
     }
-    constexpr int LB = 4;  // 16-B list loads in flight per thread (more: the kernel spills)
+    // 16-B list loads in flight per thread: LB of the current batch and, in
+    // the loop, LB of the next one.  6 covers config 4's round (24 pods x 72
+    // entries = 864 vectors, 192 loader threads) in one batch.
+    constexpr int LB = 6;
     const uint4 *L4 = reinterpret_cast<const uint4 *>(L);  // list buffers are 16-B aligned
     const int32_t n16 = (tot + 1) >> 1;
     auto put = [&](int32_t e, uint64_t v) {
@@ -2066,55 +2105,67 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
         Lk[j * kp + q] = v;
       }
     };
+    auto put2 = [&](int32_t x, const uint4 &w) {
+      if (x < n16) {
+        put(2 * x, ((uint64_t)w.y << 32) | w.x);
+        put(2 * x + 1, ((uint64_t)w.w << 32) | w.z);
+      }
+    };
     uint4 lv[LB];
 #pragma unroll
     for (int u = 0; u < LB; u++)
-      if (tid + u * nth < n16) lv[u] = L4[tid + u * nth];
+      if (u * nth < n16) lv[u] = L4[min(tid + u * nth, n16 - 1)];
+    const uint4 *psrc = reinterpret_cast<const uint4 *>(pods + rp0);
+    uint4 *pdst = reinterpret_cast<uint4 *>(Lp);
+    const int32_t p16 = rn * (int32_t)(sizeof(DevPod) / 16);
+    // four pod vectors per thread, named (an array here went to scratch)
+    uint4 a0, a1, a2, a3;
+    a0 = psrc[min(tid, p16 - 1)];
+    if (nth < p16) a1 = psrc[min(tid + nth, p16 - 1)];
+    if (2 * nth < p16) a2 = psrc[min(tid + 2 * nth, p16 - 1)];
+    if (3 * nth < p16) a3 = psrc[min(tid + 3 * nth, p16 - 1)];
+    // ---- trip B (waits for the head entries alone: they were issued first)
+    int32_t nd[2];
+    NV v[2];
 #pragma unroll
-    for (int u = 0; u < LB; u++) {
-      const int32_t x = tid + u * nth;
-      if (x < n16) {
-        put(2 * x, ((uint64_t)lv[u].y << 32) | lv[u].x);
-        put(2 * x + 1, ((uint64_t)lv[u].w << 32) | lv[u].z);
-      }
+    for (int u = 0; u < 2; u++) {
+      nd[u] = (hv[u] && he[u] != 0) ? key_node(he[u]) : -1;
+      if (u * nth < RES_PRE)
+        if (nd[u] >= 0) load_row(v[u], nodes(), nd[u]);
     }
-    NV v[2];  // (issued after the first list batch's stores: both at once spill)
+    // ---- trip A's stores; further list batches
+    for (int32_t b = 0;;) {
+      const int32_t nb = b + LB * nth;
+      const bool more = nb < n16;  // wave-uniform
+      uint4 nx[LB];
+      if (more) {
 #pragma unroll
-    for (int u = 0; u < 2; u++)
-      if (nd[u] >= 0) load_row(v[u], nodes(), nd[u]);
-    for (int32_t x0 = tid + LB * nth; x0 < n16; x0 += LB * nth) {  // rounds whose lists exceed one batch
-#pragma unroll
-      for (int u = 0; u < LB; u++)
-        if (x0 + u * nth < n16) lv[u] = L4[x0 + u * nth];
-#pragma unroll
-      for (int u = 0; u < LB; u++) {
-        const int32_t x = x0 + u * nth;
-        if (x < n16) {
-          put(2 * x, ((uint64_t)lv[u].y << 32) | lv[u].x);
-          put(2 * x + 1, ((uint64_t)lv[u].w << 32) | lv[u].z);
-        }
+        for (int u = 0; u < LB; u++)
+          if (nb + u * nth < n16) nx[u] = L4[min(nb + tid + u * nth, n16 - 1)];
       }
+#pragma unroll
+      for (int u = 0; u < LB; u++) put2(b + tid + u * nth, lv[u]);
+      if (!more) break;
+#pragma unroll
+      for (int u = 0; u < LB; u++) lv[u] = nx[u];
+      b = nb;
     }
     for (int32_t x = tid; x < rn * (kp - k); x += nth) {  // zero padding of each row up to kp
       const int32_t j = x / (kp - k), q = k + x - j * (kp - k);
       Lk[j * kp + q] = 0ull;
     }
-    {
-      const uint4 *src = reinterpret_cast<const uint4 *>(pods + rp0);
-      uint4 *dst = reinterpret_cast<uint4 *>(Lp);
-      const int32_t p16 = rn * (int32_t)(sizeof(DevPod) / 16);
-      // four loads in flight per thread, named (an array here went to scratch)
-      for (int32_t x0 = tid; x0 < p16; x0 += 4 * nth) {
-        const int32_t x1 = x0 + nth, x2 = x0 + 2 * nth, x3 = x0 + 3 * nth;
-        const uint4 a0 = src[x0];
-        const uint4 a1 = x1 < p16 ? src[x1] : a0;
-        const uint4 a2 = x2 < p16 ? src[x2] : a0;
-        const uint4 a3 = x3 < p16 ? src[x3] : a0;
-        dst[x0] = a0;
-        if (x1 < p16) dst[x1] = a1;
-        if (x2 < p16) dst[x2] = a2;
-        if (x3 < p16) dst[x3] = a3;
-      }
+    if (tid < p16) pdst[tid] = a0;
+    if (tid + nth < p16) pdst[tid + nth] = a1;
+    if (tid + 2 * nth < p16) pdst[tid + 2 * nth] = a2;
+    if (tid + 3 * nth < p16) pdst[tid + 3 * nth] = a3;
+    for (int32_t b = 4 * nth; b < p16; b += 4 * nth) {  // more pod vectors (one loader wave, > 42 pods)
+      const int32_t x0 = b + tid, x1 = x0 + nth, x2 = x0 + 2 * nth, x3 = x0 + 3 * nth;
+      const uint4 c0 = psrc[min(x0, p16 - 1)], c1 = psrc[min(x1, p16 - 1)], c2 = psrc[min(x2, p16 - 1)],
+                  c3 = psrc[min(x3, p16 - 1)];
+      if (x0 < p16) pdst[x0] = c0;
+      if (x1 < p16) pdst[x1] = c1;
+      if (x2 < p16) pdst[x2] = c2;
+      if (x3 < p16) pdst[x3] = c3;
     }
 #pragma unroll
     for (int u = 0; u < 2; u++) {

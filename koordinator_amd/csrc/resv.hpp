@@ -90,26 +90,26 @@ __device__ __forceinline__ void load_resv(NumaRowRS<S> &r, const DevResv &d, int
   for (int q = 0; q < S; q++) {
     ResvSlot &x = r.rs[q];
     const size_t at = (size_t)q * (size_t)d.stride + (size_t)i;
-    x.rf = q < d.slots ? d.flags[at] : 0u;
+    x.rf = q < d.slots ? as_global(d.flags)[at] : 0u;
     x.rn = 0;
     x.rk = 0;
     x.rdev = 0;
 #pragma unroll
     for (int k = 0; k < 2; k++) x.ra[k] = x.rd[k] = x.rz[k] = 0.0;
     if (x.rf & KOORDHIP_RESV_PRESENT) {
-      x.rn = d.rn[at];
-      x.rk = d.rank[at];
+      x.rn = as_global(d.rn)[at];
+      x.rk = as_global(d.rank)[at];
 #pragma unroll
       for (int k = 0; k < 2; k++) {
-        x.ra[k] = d.ra[k][at];
-        x.rd[k] = d.rd[k][at];
-        x.rz[k] = d.rz[k][at];
+        x.ra[k] = as_global(d.ra[k])[at];
+        x.rd[k] = as_global(d.rd[k])[at];
+        x.rz[k] = as_global(d.rz[k])[at];
       }
     }
     if constexpr (S > 1) {
       const bool on = d.rc[0] != nullptr && (x.rf & KOORDHIP_RESV_PRESENT);
 #pragma unroll
-      for (int w = 0; w < NW; w++) rcm_of(r, q)[w] = on ? d.rc[w][at] : 0ull;
+      for (int w = 0; w < NW; w++) rcm_of(r, q)[w] = on ? as_global(d.rc[w])[at] : 0ull;
     }
   }
 }
@@ -138,13 +138,13 @@ __device__ __forceinline__ void store_resv_wt(const NumaRowRS<S> &r, const DevRe
     const ResvSlot &x = r.rs[q];
     if (!(x.rf & KOORDHIP_RESV_PRESENT)) continue;
     const size_t at = (size_t)q * (size_t)d.stride + (size_t)i;
-    st_wt(&d.rd[0][at], x.rd[0]);
-    st_wt(&d.rd[1][at], x.rd[1]);
-    st_wt(&d.rn[at], x.rn);
+    st_wt_g(&d.rd[0][at], x.rd[0]);
+    st_wt_g(&d.rd[1][at], x.rd[1]);
+    st_wt_g(&d.rn[at], x.rn);
     if constexpr (S > 1) {
       if (d.rc[0])
 #pragma unroll
-        for (int w = 0; w < NW; w++) st_wt(&d.rc[w][at], rcm_of(r, q)[w]);
+        for (int w = 0; w < NW; w++) st_wt_g(&d.rc[w][at], rcm_of(r, q)[w]);
     }
   }
 }
