@@ -46,6 +46,11 @@
  *                              read by frameworkext/eventhandlers/reservation_handler.go:92-94 and handed to every
  *                              PostFilter (elasticquota/plugin.go:310, reservation/plugin.go:496,
  *                              coscheduling/core/core.go:289-293)
+ *   koordhip_diagnose_reasons / koordhip_node_reasons / koordhip_fetch_reasons / koordhip_fetch_node_reasons
+ *                           <- the Status reason and code behind each of those nodes: fitsRequest's
+ *                              InsufficientResource list ((upstream) fit.go), nodenumaresource/plugin.go:266-363 and
+ *                              resource_manager.go:244-326,442-453, reservation/plugin.go:373-440; what
+ *                              FitError.Error() prints and nodesWherePreemptionMightHelp drops
  *   koordhip_place_stream_ext / koordhip_eval_ext
  *                           <- the exact sequential cycle for profiles with plugins whose scores are normalized
  *                              over the feasible nodes (DefaultNormalizeScore, upstream helper/normalize_score.go)
@@ -741,6 +746,97 @@ int koordhip_diagnose_ext(koordhip_ctx *ctx, const koordhip_pod *pods, const koo
  * evaluated), without its score planes and per-call buffers. */
 int koordhip_node_status_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const koordhip_pod_ext *ext,
                              uint16_t *status /* [n] */);
+
+/* ---- FitError reasons per node (additive to ABI 15: detect it by the symbols)
+ * What upstream's FitError.Error() prints is a histogram of Status REASONS, not
+ * of plugin names, and PostFilter's nodesWherePreemptionMightHelp drops the
+ * nodes whose status code is UnschedulableAndUnresolvable.  A reason is a bit
+ * index; the code (U = Unschedulable, UU = UnschedulableAndUnresolvable, E =
+ * Error) is fixed per reason.
+ *
+ *   slot name                  reference string / site                       code
+ *    0   STATIC                NodeUnschedulable / NodeAffinity /            UU
+ *                              TaintToleration (the host-resolved class bit)
+ *    1   FIT_PODS              "Too many pods"                               U
+ *    2   FIT_CPU               "Insufficient cpu"                            U
+ *    3   FIT_MEM               "Insufficient memory"                         U
+ *    4   FIT_EPH               "Insufficient ephemeral-storage"              U
+ *    5   FIT_BCPU              "Insufficient kubernetes.io/batch-cpu"        U
+ *    6   FIT_BMEM              "Insufficient kubernetes.io/batch-memory"     U
+ *    7   LA_USAGE              load_aware.go:45-46 (one slot)                U
+ *    8   NUMA_POD_ERROR        plugin.go:244 (KOORDHIP_POD_NUMA_ERROR)       E
+ *    9   NUMA_AMP_CPU          ErrInsufficientAmplifiedCPU, plugin.go:360    U
+ *   10   NUMA_NO_TOPOLOGY      ErrNotFoundCPUTopology / ErrInvalidCPUTopology UU
+ *                              plugin.go:286,293
+ *   11   NUMA_SMT_ALIGN        ErrSMTAlignmentError, plugin.go:298           UU
+ *   12   NUMA_FULL_PCPUS_ONLY  ErrRequiredFullPCPUsPolicy, plugin.go:303     UU
+ *   13   NUMA_CPUS             "not enough cpus available to satisfy         U
+ *                              request", resource_manager.go:258
+ *   14   NUMA_REQUIRED_POLICY  "insufficient CPUs to satisfy required cpu    U
+ *                              bind policy", resource_manager.go:450
+ *   15   NUMA_NO_ZONES         "node(s) missing NUMA resources",             UU
+ *                              topology_hint.go:36
+ *   16   NUMA_POLICY           Admit / Allocate fails on a topology-policy   U
+ *                              node (one slot)
+ *   17   RESV_AFFINITY         ErrReasonReservationAffinity                  UU
+ *   18   RESV_INSUFFICIENT     ErrReasonReservationInsufficientResources     U
+ *   19-31 reserved, zero (DeviceShare, extended scalars, PodTopologySpread,
+ *        InterPodAffinity)
+ *
+ * NodeResourcesFit reports every failing resource of fitsRequest; every other
+ * plugin reports one reason, the reference's first exit. */
+#define KOORDHIP_REASON_STATIC 0
+#define KOORDHIP_REASON_FIT_PODS 1
+#define KOORDHIP_REASON_FIT_CPU 2
+#define KOORDHIP_REASON_FIT_MEM 3
+#define KOORDHIP_REASON_FIT_EPH 4
+#define KOORDHIP_REASON_FIT_BCPU 5
+#define KOORDHIP_REASON_FIT_BMEM 6
+#define KOORDHIP_REASON_LA_USAGE 7
+#define KOORDHIP_REASON_NUMA_POD_ERROR 8
+#define KOORDHIP_REASON_NUMA_AMP_CPU 9
+#define KOORDHIP_REASON_NUMA_NO_TOPOLOGY 10
+#define KOORDHIP_REASON_NUMA_SMT_ALIGN 11
+#define KOORDHIP_REASON_NUMA_FULL_PCPUS_ONLY 12
+#define KOORDHIP_REASON_NUMA_CPUS 13
+#define KOORDHIP_REASON_NUMA_REQUIRED_POLICY 14
+#define KOORDHIP_REASON_NUMA_NO_ZONES 15
+#define KOORDHIP_REASON_NUMA_POLICY 16
+#define KOORDHIP_REASON_RESV_AFFINITY 17
+#define KOORDHIP_REASON_RESV_INSUFFICIENT 18
+#define KOORDHIP_REASON_COUNT 19
+#define KOORDHIP_REASON_SLOTS 32
+/* the reasons of each KOORDHIP_ST_* bit (a status bit is set iff one of its reasons is) */
+#define KOORDHIP_REASONS_OF_STATIC 0x00000001u
+#define KOORDHIP_REASONS_OF_FIT 0x0000007Eu
+#define KOORDHIP_REASONS_OF_LA 0x00000080u
+#define KOORDHIP_REASONS_OF_NUMA 0x0001FF00u
+#define KOORDHIP_REASONS_OF_RESV 0x00060000u
+/* the reasons whose code is UnschedulableAndUnresolvable: STATIC, NUMA_NO_TOPOLOGY,
+ * NUMA_SMT_ALIGN, NUMA_FULL_PCPUS_ONLY, NUMA_NO_ZONES, RESV_AFFINITY */
+#define KOORDHIP_REASON_UNRESOLVABLE_MASK 0x00029C01u
+/* ... and Error: NUMA_POD_ERROR */
+#define KOORDHIP_REASON_ERROR_MASK 0x00000100u
+
+typedef struct koordhip_reasons { /* 264 B */
+  int32_t feasible;               /* nodes with no reason set */
+  int32_t unresolvable;           /* nodes whose FIRST failing plugin reports a UU reason */
+  int32_t first[KOORDHIP_REASON_SLOTS]; /* nodes whose first failing plugin (the order of koordhip_diag.first) reports
+                                            reason r: the histogram FitError.Error() prints */
+  int32_t any[KOORDHIP_REASON_SLOTS];   /* nodes where reason r holds, every plugin evaluated */
+} koordhip_reasons;
+
+/* koordhip_diagnose's call with reason records: the current state, the same
+ * envelope, error codes and "writes no engine state" rule. */
+int koordhip_diagnose_reasons(koordhip_ctx *ctx, const koordhip_pod *pods, int32_t n_pods, koordhip_reasons *out);
+/* One pod on the current state: mask[i] = the reasons of every failing plugin
+ * on node i (the `any` view; the first plugin and the code follow from it). */
+int koordhip_node_reasons(koordhip_ctx *ctx, const koordhip_pod *pod, uint32_t *mask /* [n] */);
+/* koordhip_fetch_diagnosis' call with reason records: the last place call's
+ * unplaced pods at their decision states; same envelope and validity rule. */
+int koordhip_fetch_reasons(koordhip_ctx *ctx, koordhip_reasons *out /* [n_pods] */, int32_t n_pods);
+/* koordhip_fetch_node_status' call with reason masks. */
+int koordhip_fetch_node_reasons(koordhip_ctx *ctx, int32_t pod_index, uint32_t *mask /* [n] */);
 
 /* ---- preemption dry run (additive to ABI 15: detect it by the symbols) -----
  * The PostFilter of elasticquota/plugin.go:310-329: SelectVictimsOnNode

@@ -238,6 +238,47 @@ FILTER_ORDER = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_LA_FAIL, ST_NUMA_FAIL, ST_RESV_F
 FILTER_ORDER_EXT = (ST_STATIC_FAIL, ST_FIT_FAIL, ST_XFIT_FAIL, ST_PTS_FAIL, ST_IPA_FAIL, ST_LA_FAIL, ST_NUMA_FAIL,
                     ST_DEVICE_FAIL, ST_RESV_FAIL)
 DIAG_EXT_POD_TILE = 32  # pods per workgroup of koordhip_diagnose_ext's kernel (diag_ext.hip DIAGX_PT)
+# FitError reasons (KOORDHIP_REASON_*, include/koordhip.h): bit indices of a node's 32-bit reason mask
+(REASON_STATIC, REASON_FIT_PODS, REASON_FIT_CPU, REASON_FIT_MEM, REASON_FIT_EPH, REASON_FIT_BCPU, REASON_FIT_BMEM,
+ REASON_LA_USAGE, REASON_NUMA_POD_ERROR, REASON_NUMA_AMP_CPU, REASON_NUMA_NO_TOPOLOGY, REASON_NUMA_SMT_ALIGN,
+ REASON_NUMA_FULL_PCPUS_ONLY, REASON_NUMA_CPUS, REASON_NUMA_REQUIRED_POLICY, REASON_NUMA_NO_ZONES, REASON_NUMA_POLICY,
+ REASON_RESV_AFFINITY, REASON_RESV_INSUFFICIENT) = range(19)
+REASON_COUNT, REASON_SLOTS = 19, 32
+# the reasons of each status bit: a status bit is set iff one of its reasons is
+REASONS_OF_BIT = {
+    ST_STATIC_FAIL: 0x00000001,
+    ST_FIT_FAIL: 0x0000007E,
+    ST_LA_FAIL: 0x00000080,
+    ST_NUMA_FAIL: 0x0001FF00,
+    ST_RESV_FAIL: 0x00060000,
+}
+REASON_UNRESOLVABLE_MASK = 0x00029C01   # the UnschedulableAndUnresolvable reasons
+REASON_ERROR_MASK = 0x00000100          # the Error reason (NUMA_POD_ERROR)
+# numpy twin of koordhip_reasons (264 bytes)
+REASONS_DTYPE = np.dtype([("feasible", "<i4"), ("unresolvable", "<i4"), ("first", "<i4", (REASON_SLOTS,)),
+                          ("any", "<i4", (REASON_SLOTS,))])
+assert REASONS_DTYPE.itemsize == 264
+
+
+def reasons_status(mask):
+    """The KOORDHIP_ST_* bits a reason mask (int or array) stands for."""
+    st = 0
+    for bit, group in REASONS_OF_BIT.items():
+        st = st | np.where((np.asarray(mask, np.uint32) & np.uint32(group)) != 0, np.uint32(bit), np.uint32(0))
+    return st
+
+
+def first_reasons(mask):
+    """The reasons of the first failing plugin (FILTER_ORDER) of a reason mask (int or array)."""
+    m = np.asarray(mask, np.uint32)
+    out = np.zeros_like(m)
+    done = np.zeros(m.shape, bool)
+    for bit in FILTER_ORDER:
+        g = m & np.uint32(REASONS_OF_BIT[bit])
+        take = ~done & (g != 0)
+        out = np.where(take, g, out)
+        done |= take
+    return out
 # the preemption dry run (koordhip_preempt*): numpy twins of koordhip_assigned (160 bytes),
 # koordhip_preemptor (208), koordhip_preempt_node (32) and koordhip_preempt_result (56)
 PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
@@ -307,7 +348,8 @@ class KoordhipError(RuntimeError):
 
 _lib = None
 # additive to ABI 15 (no version bump): a build without them still loads
-ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext")
+ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext", "koordhip_diagnose_reasons",
+                    "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons")
 
 
 def load_library(path: str = LIB_PATH):
@@ -357,6 +399,10 @@ def load_library(path: str = LIB_PATH):
         "koordhip_fetch_node_status": (C.c_int, [vp, C.c_int32, _u8p]),
         "koordhip_diagnose_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp]),
         "koordhip_node_status_ext": (C.c_int, [vp, vp, vp, C.POINTER(C.c_uint16)]),
+        "koordhip_diagnose_reasons": (C.c_int, [vp, vp, C.c_int32, vp]),
+        "koordhip_node_reasons": (C.c_int, [vp, vp, C.POINTER(C.c_uint32)]),
+        "koordhip_fetch_reasons": (C.c_int, [vp, vp, C.c_int32]),
+        "koordhip_fetch_node_reasons": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_uint32)]),
         "koordhip_preempt_load_pods": (C.c_int, [vp, vp, C.c_int32, _i32p, C.c_int32]),
         "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
@@ -397,6 +443,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_commit_ext", "koordhip_uncommit_ext",
     "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
     "koordhip_diagnose_ext", "koordhip_node_status_ext",
+    "koordhip_diagnose_reasons", "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_preempt_stream",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",

@@ -22,6 +22,7 @@
 #include "cls.h"
 #include "diag.h"
 #include "diag_ext.h"
+#include "reasons.h"
 #include "preempt.h"
 #include "kernels.h"
 #include "place_plan.hpp"
@@ -3481,6 +3482,105 @@ int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *stat
   HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
                                  static_cast<uint8_t *>(c->d_diag_rec), c->stream));
   HIP_TRY(hipMemcpyAsync(status, c->d_diag_rec, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// ---- FitError reasons (reasons.hip) ------------------------------------------
+// The four calls mirror koordhip_diagnose, koordhip_fetch_diagnosis and
+// koordhip_fetch_node_status: their checks, workspaces and error codes, with
+// koordhip_reasons records / 32-bit reason masks in place of koordhip_diag
+// records / status bytes.
+
+static int reasons_current(koordhip_ctx *c, const char *who, const koordhip_pod *pods, int32_t n_pods,
+                           koordhip_reasons *out, uint32_t *mask) {
+  static_assert(sizeof(koordhip_reasons) == 264, "koordhip_reasons is 66 int32 counters");
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  bool reserve = false;
+  if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
+  if (c->seq)
+    return fail(KOORDHIP_EINVAL, std::string(who) + ": the profile / snapshot evaluates in the sequential cycle "
+                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
+  if (reserve) return fail(KOORDHIP_EINVAL, std::string(who) + ": reserve / reservation-operating-mode pods are not covered");
+  std::vector<kh::DevPod> hp;
+  if (int e = to_dev_pods(pods, n_pods, hp)) return e;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t rb = mask ? (size_t)c->n * sizeof(uint32_t) : (size_t)n_pods * sizeof(koordhip_reasons);
+  if (rb == 0) return 0;
+  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, (size_t)n_pods * sizeof(kh::DevPod))) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), (size_t)n_pods * sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  HIP_TRY(kh::launch_reasons(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods), n_pods,
+                             mask ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
+                             mask ? static_cast<uint32_t *>(c->d_diag_rec) : nullptr, c->stream));
+  HIP_TRY(hipMemcpyAsync(mask ? static_cast<void *>(mask) : static_cast<void *>(out), c->d_diag_rec, rb,
+                         hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int koordhip_diagnose_reasons(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_pods, koordhip_reasons *out) {
+  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
+  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
+  if (n_pods == 0) return 0;
+  return reasons_current(c, "koordhip_diagnose_reasons", pods, n_pods, out, nullptr);
+}
+
+int koordhip_node_reasons(koordhip_ctx *c, const koordhip_pod *pod, uint32_t *mask) {
+  if (!c || !pod || !mask) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return reasons_current(c, "koordhip_node_reasons", pod, 1, nullptr, mask);
+}
+
+int koordhip_fetch_reasons(koordhip_ctx *c, koordhip_reasons *out, int32_t n_pods) {
+  if (!c || (!out && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
+  if (int e = diag_replay_ready(c)) return e;
+  if (n_pods > c->n_staged) return fail(KOORDHIP_EINVAL, "n_pods exceeds the staged stream");
+  if (n_pods == 0) return 0;
+  // the lists cover the whole stream: the commits of pods >= n_pods are un-applied too
+  const int32_t P = c->n_staged, n = c->n;
+  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
+  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
+  const kh::DiagLists l = kh::diag_lists(ws, n, P);
+  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
+  int32_t U = 0;
+  HIP_TRY(hipMemcpyAsync(&U, l.tot + 1, sizeof(U), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_reasons));
+  if (U <= 0) return 0;
+  const size_t rb = (size_t)U * sizeof(koordhip_reasons);
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  HIP_TRY(kh::launch_reasons_replay(c->dc, c->d, c->d_pods, c->d_cpus, l, U, -1, static_cast<int32_t *>(c->d_diag_rec),
+                                    nullptr, c->stream));
+  std::vector<koordhip_reasons> rec((size_t)U);
+  std::vector<int32_t> ul((size_t)U);
+  HIP_TRY(hipMemcpyAsync(rec.data(), c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(ul.data(), l.ul, (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  for (int32_t k = 0; k < U; k++)
+    if (ul[k] >= 0 && ul[k] < n_pods) out[ul[k]] = rec[k];
+  return 0;
+}
+
+int koordhip_fetch_node_reasons(koordhip_ctx *c, int32_t pod_index, uint32_t *mask) {
+  if (!c || !mask) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (int e = diag_replay_ready(c)) return e;
+  if (pod_index < 0 || pod_index >= c->n_staged) return fail(KOORDHIP_EINVAL, "pod_index outside the staged stream");
+  int32_t node = 0;
+  HIP_TRY(hipMemcpy(&node, c->d_out + pod_index, sizeof(node), hipMemcpyDeviceToHost));
+  if (node >= 0) return fail(KOORDHIP_EINVAL, "the pod was placed: it has no unschedulable status");
+  const int32_t P = c->n_staged, n = c->n;
+  if (n == 0) return 0;
+  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, (size_t)n * sizeof(uint32_t))) return e;
+  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
+  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
+  HIP_TRY(kh::launch_reasons_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
+                                    static_cast<uint32_t *>(c->d_diag_rec), c->stream));
+  HIP_TRY(hipMemcpyAsync(mask, c->d_diag_rec, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -8,7 +8,8 @@
 //                     an LDS table of whole records, the workgroup flushes its
 //                     non-zero entries with one atomic per counter (lanes on
 //                     consecutive words of a pod's record).
-//   k_diag_replay     the unplaced pods of the last place call at their
+//   k_diag_replay     (the template of diag_replay.hpp, here with the status
+//                     kind) the unplaced pods of the last place call at their
 //                     decision states, without a copy of the table: a commit
 //                     is exactly invertible (apply_delta / numa_apply with
 //                     sign -1, integers held in f64, order-independent), so a
@@ -25,17 +26,14 @@
 #include <algorithm>
 
 #include "diag.h"
+#include "diag_replay.hpp"
 #include "eval.hpp"
 
 namespace kh {
 
-constexpr int DIAG_THREADS = 256;
-constexpr int DIAG_PT = 32;                 // pods per LDS tile
-constexpr int DIAG_POD_WORDS = (int)(sizeof(DevPod) / sizeof(uint64_t));
 constexpr int DIAG_ANY = (int)(offsetof(koordhip_diag, any) / sizeof(int32_t));
 constexpr int DIAG_FIRST = (int)(offsetof(koordhip_diag, first) / sizeof(int32_t));
 constexpr int DIAG_NBITS = 5;               // the status bits these kernels produce: FIT, LA, NUMA, RESV, STATIC
-static_assert(sizeof(DevPod) % sizeof(uint64_t) == 0, "pod records are staged as 8-B words");
 static_assert(offsetof(koordhip_diag, feasible) == 0 && kDiagWords == 2 + 2 * KOORDHIP_DIAG_BITS, "record layout");
 static_assert((KOORDHIP_ST_FIT_FAIL | KOORDHIP_ST_LA_FAIL | KOORDHIP_ST_NUMA_FAIL | KOORDHIP_ST_RESV_FAIL |
                KOORDHIP_ST_STATIC_FAIL) == (1u << DIAG_NBITS) - 1u, "the counted status bits are bits 0..4");
@@ -72,13 +70,19 @@ __device__ __forceinline__ void diag_count(uint32_t st, bool live, uint32_t bits
   }
 }
 
-// the workgroup's LDS records of np pods -> out (np contiguous records)
-__device__ __forceinline__ void diag_flush(const int32_t *tab, int32_t np, int32_t *out) {
-  for (int32_t w = threadIdx.x; w < np * kDiagWords; w += DIAG_THREADS) {
-    const int32_t x = tab[w];
-    if (x) atomicAdd(&out[w], x);
+// the replay's kind (diag_replay.hpp): the status bits into a koordhip_diag, or one pod's status bytes
+struct DiagStatus {
+  static constexpr int WORDS = kDiagWords;
+  using Plane = uint8_t;
+  static __device__ __forceinline__ uint32_t slots(const DevCfg &c) { return status_bits(c); }
+  static __device__ __forceinline__ uint32_t eval(const DevCfg &c, const DevPod &pod, const NV &v, const NumaRowR &nr,
+                                                  const DevNumaClass *classes) {
+    return filter_status(c, pod, v, nr, classes, 0, 0u);
   }
-}
+  static __device__ __forceinline__ void count(uint32_t st, bool live, uint32_t bits, int32_t *rec) {
+    diag_count(st, live, bits, rec);
+  }
+};
 
 // ---------------------------------------------------------------------------
 // k_diag: S = the reservation slots of the side row (1: no reservation columns)
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag(DevCfg c, DevNodes d, con
     diag_count(st, live, bits, tab + q * kDiagWords);
   }
   __syncthreads();
-  diag_flush(tab, np, out + (size_t)p0 * kDiagWords);
+  diag_flush<kDiagWords>(tab, np, out + (size_t)p0 * kDiagWords);
 }
 
 // ---------------------------------------------------------------------------
@@ -208,77 +212,6 @@ __global__ void k_diag_sort(const int32_t *__restrict__ off, int32_t *__restrict
 }
 
 // ---------------------------------------------------------------------------
-// k_diag_replay: workgroup (x, y) takes nodes [256 x, 256 x + 256) and the
-// tiles [y tpb, (y + 1) tpb) of the unplaced list, last tile first.  The loop
-// over the unplaced pods is wave-uniform (the ballots are valid); only the
-// walk over a node's commits diverges.
-
-__global__ __launch_bounds__(DIAG_THREADS) void k_diag_replay(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
-                                                              const uint64_t *__restrict__ cpus,
-                                                              const int32_t *__restrict__ off,
-                                                              const int32_t *__restrict__ nl,
-                                                              const int32_t *__restrict__ ul, int32_t U, int32_t single,
-                                                              int32_t tpb, int32_t *__restrict__ out,
-                                                              uint8_t *__restrict__ status) {
-  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAG_PT * DIAG_POD_WORDS];
-  __shared__ int32_t su[DIAG_PT];
-  __shared__ int32_t tab[DIAG_PT * kDiagWords];
-  const int t = threadIdx.x;
-  const int32_t i = (int32_t)blockIdx.x * DIAG_THREADS + t;
-  const bool live = i < d.n;
-  const int32_t il = live ? i : d.n - 1;
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
-  NumaRowR nr{};
-  load_numa<true>(nr, d, il, all);
-  const int32_t lo = live ? off[il] : 0;
-  int32_t ptr = live ? off[il + 1] : 0;  // this node's commits nl[ptr ..) are un-applied
-  const bool numa = numa_on(c) && cpus != nullptr;
-  const uint32_t bits = status_bits(c);
-  const DevPod *sp = reinterpret_cast<const DevPod *>(spw);
-  const int32_t ntiles = (U + DIAG_PT - 1) / DIAG_PT;
-  const int32_t ty0 = (int32_t)blockIdx.y * tpb, ty1 = min(ntiles, ty0 + tpb);
-  for (int32_t tile = ty1 - 1; tile >= ty0; tile--) {
-    const int32_t k0 = tile * DIAG_PT, nk = min(DIAG_PT, U - k0);
-    __syncthreads();  // the previous tile's flush has read tab
-    if (t < nk) su[t] = single >= 0 ? single : ul[k0 + t];
-    for (int32_t w = t; w < nk * kDiagWords; w += DIAG_THREADS) tab[w] = 0;
-    __syncthreads();
-    for (int32_t w = t; w < nk * DIAG_POD_WORDS; w += DIAG_THREADS) {
-      const int32_t q = w / DIAG_POD_WORDS;
-      spw[w] = reinterpret_cast<const uint64_t *>(pods + su[q])[w - q * DIAG_POD_WORDS];
-    }
-    __syncthreads();
-    for (int32_t q = nk - 1; q >= 0; q--) {
-      const int32_t pu = su[q];
-      while (ptr > lo) {  // Unreserve this node's commits made after pod pu's decision
-        const int32_t j = nl[ptr - 1];
-        if (j < pu) break;
-        ptr--;
-        const DevPod pj = pods[j];
-        apply_delta(v, pj, -1);
-        if (numa && is_cpuset(pj)) {
-          uint64_t m[NW];
-#pragma unroll
-          for (int w = 0; w < NW; w++) m[w] = cpus[(size_t)j * NW + w];
-          numa_apply(nr, pj, m, -1);
-        }
-      }
-      const DevPod pod = sp[q];
-      const uint32_t st = filter_status(c, pod, v, nr, d.nu.cls, 0, 0u);
-      if (status) {
-        if (live) status[i] = (uint8_t)st;
-      } else {
-        diag_count(st, live, bits, tab + q * kDiagWords);
-      }
-    }
-    __syncthreads();
-    if (!status) diag_flush(tab, nk, out + (size_t)k0 * kDiagWords);
-  }
-}
-
-// ---------------------------------------------------------------------------
 // host-side launch wrappers
 
 hipError_t launch_diag(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t *out,
@@ -334,17 +267,7 @@ hipError_t launch_diag_lists(int32_t *ws, const int32_t *out_node, int32_t P, in
 hipError_t launch_diag_replay(const DevCfg &c, const DevNodes &d, const DevPod *pods, const uint64_t *cpus,
                               const DiagLists &l, int32_t U, int32_t single, int32_t *out, uint8_t *status,
                               hipStream_t s) {
-  if (U <= 0 || d.n <= 0) return hipSuccess;
-  if (c.resv || c.zones) return hipErrorInvalidValue;  // their Reserve is not invertible from what the engine keeps
-  if ((single >= 0 && U != 1) || (status && single < 0) || (!status && !out)) return hipErrorInvalidValue;
-  const int32_t gx = (d.n + DIAG_THREADS - 1) / DIAG_THREADS;
-  const int32_t ntiles = (U + DIAG_PT - 1) / DIAG_PT;
-  // enough workgroups to fill the device; a workgroup's later tiles go on from the row state of its earlier ones
-  const int32_t gy = std::max(1, std::min(ntiles, std::min(65535, (1024 + gx - 1) / gx)));
-  const int32_t tpb = (ntiles + gy - 1) / gy;
-  hipLaunchKernelGGL(k_diag_replay, dim3(gx, (ntiles + tpb - 1) / tpb), dim3(DIAG_THREADS), 0, s, c, d, pods, cpus, l.off,
-                     l.nl, l.ul, U, single, tpb, out, status);
-  return hipGetLastError();
+  return launch_replay<DiagStatus>(c, d, pods, cpus, l, U, single, out, status, s);
 }
 
 }  // namespace kh

@@ -919,4 +919,76 @@ __device__ __forceinline__ uint32_t filter_status(const DevCfg &c, const DevPod 
   return b;
 }
 
+// The KOORDHIP_REASON_* bits of one (pod, node): filter_status' plugins, each
+// saying why.  NodeResourcesFit reports every failing term of fit_filter (as
+// fitsRequest collects one InsufficientResource each); every other plugin
+// reports the reference's first exit.  A status bit is set iff one of its
+// KOORDHIP_REASONS_OF_* bits is (pinned by the reasons tests, not by this
+// comment).
+constexpr uint32_t reason_bit(int r) { return 1u << r; }
+
+__device__ __forceinline__ uint32_t fit_reasons(const DevPod &p, const NV &v) {
+  uint32_t m = v.npods < v.a_pods ? 0u : reason_bit(KOORDHIP_REASON_FIT_PODS);
+  if (!(p.flags & KOORDHIP_POD_HAS_REQ)) return m;
+  auto over = [&](int r) { return p.req[r] > v.a[r] - v.r[r]; };
+  if (p.req[KOORDHIP_RES_CPU] != 0.0 ? over(KOORDHIP_RES_CPU) : (v.flags & NF_OVER_CPU) != 0)
+    m |= reason_bit(KOORDHIP_REASON_FIT_CPU);
+  if (p.req[KOORDHIP_RES_MEM] != 0.0 ? over(KOORDHIP_RES_MEM) : (v.flags & NF_OVER_MEM) != 0)
+    m |= reason_bit(KOORDHIP_REASON_FIT_MEM);
+  if (p.req[KOORDHIP_RES_EPH] != 0.0 ? over(KOORDHIP_RES_EPH) : (v.flags & NF_OVER_EPH) != 0)
+    m |= reason_bit(KOORDHIP_REASON_FIT_EPH);
+  if ((p.flags & KOORDHIP_POD_REQ_BCPU) && over(KOORDHIP_RES_BCPU)) m |= reason_bit(KOORDHIP_REASON_FIT_BCPU);
+  if ((p.flags & KOORDHIP_POD_REQ_BMEM) && over(KOORDHIP_RES_BMEM)) m |= reason_bit(KOORDHIP_REASON_FIT_BMEM);
+  return m;
+}
+
+// NodeNUMAResource: the PreFilter error, filterAmplifiedCPUs (plugin.go:272),
+// then numa_filter's exits top to bottom (plugin.go:280-320).  Inside
+// Allocate (resource_manager.go:244-326) too few free CPUs is :258; with
+// enough of them takeCPUs succeeds and only satisfiedRequiredCPUBindPolicy
+// (:442-453) is left to fail.
+__device__ __forceinline__ uint32_t numa_reason(const DevCfg &c, const DevPod &p, const NV &v, const NumaRow &r,
+                                                const DevNumaClass *classes) {
+  if (p.flags & KOORDHIP_POD_NUMA_ERROR) return reason_bit(KOORDHIP_REASON_NUMA_POD_ERROR);
+  if (c.amp && !amp_filter_ok(p, v, r)) return reason_bit(KOORDHIP_REASON_NUMA_AMP_CPU);
+  const int tp = topo_policy(r.nflags);
+  const bool cs = (p.flags & KOORDHIP_POD_CPUSET) != 0;
+  if ((p.flags & KOORDHIP_POD_NUMA_SKIP) || (!cs && tp == 0)) return 0u;
+  if (r.cls < 0) return reason_bit(cs ? KOORDHIP_REASON_NUMA_NO_TOPOLOGY : KOORDHIP_REASON_NUMA_NO_ZONES);
+  const DevNumaClass &C = classes[r.cls];
+  const uint32_t policy = reason_bit(KOORDHIP_REASON_NUMA_POLICY);
+  if (!cs) return numa_policy_ok(C, r, p) ? 0u : policy;
+  const int req = (int)KOORDHIP_NUMA_REQUIRED(p.numa_policy);
+  const bool full_only = (r.nflags & KOORDHIP_NODE_CPUBIND_MASK) == 1u;
+  if (full_only || req == (int)KOORDHIP_CPUBIND_FULL_PCPUS) {
+    if (p.numa_cpus % C.cpc != 0) return reason_bit(KOORDHIP_REASON_NUMA_SMT_ALIGN);
+    if (full_only && (req != (int)KOORDHIP_CPUBIND_FULL_PCPUS ||
+                      (int)KOORDHIP_NUMA_PREFERRED(p.numa_policy) != (int)KOORDHIP_CPUBIND_FULL_PCPUS))
+      return reason_bit(KOORDHIP_REASON_NUMA_FULL_PCPUS_ONLY);
+  }
+  if (tp != 0) return numa_policy_ok(C, r, p) ? 0u : policy;
+  if (req == (int)KOORDHIP_CPUBIND_NONE) return 0u;
+  if (popc4(r.fr) < p.numa_cpus) return reason_bit(KOORDHIP_REASON_NUMA_CPUS);
+  return numa_alloc_ok(C, r, p) ? 0u : reason_bit(KOORDHIP_REASON_NUMA_REQUIRED_POLICY);
+}
+
+// filter_status' arguments; the 32-bit reason mask.
+template <int S>
+__device__ __forceinline__ uint32_t filter_reasons(const DevCfg &c, const DevPod &pod, const NV &v,
+                                                   const NumaRowRS<S> &r, const DevNumaClass *classes, int nmatch,
+                                                   uint32_t mm, ResvXS rx = no_rx()) {
+  uint32_t m = 0;
+  if ((c.filt & KOORDHIP_PLUGIN_NODE_STATIC) && !((v.sa >> pod.sclass) & 1u)) m |= reason_bit(KOORDHIP_REASON_STATIC);
+  if (c.filt & KOORDHIP_PLUGIN_FIT) m |= fit_reasons(pod, v);
+  if ((c.filt & KOORDHIP_PLUGIN_LOADAWARE) && !la_filter(pod, v)) m |= reason_bit(KOORDHIP_REASON_LA_USAGE);
+  if (c.filt & KOORDHIP_PLUGIN_NUMA) m |= numa_reason(c, pod, v, r, classes);
+  if (c.filt & KOORDHIP_PLUGIN_RESERVATION) {
+    if (nmatch > 0)
+      m |= resv_filter(pod, v, r, mm, nmatch, rx) ? 0u : reason_bit(KOORDHIP_REASON_RESV_INSUFFICIENT);
+    else if (pod.flags & KOORDHIP_POD_RESV_AFFINITY)
+      m |= reason_bit(KOORDHIP_REASON_RESV_AFFINITY);
+  }
+  return m;
+}
+
 }  // namespace kh

@@ -47,6 +47,51 @@ REASON_OF_BIT = {
 }
 
 
+# koordhip_reasons records (abi.REASONS_DTYPE): the reference's Status reason per slot.  The NodeResourcesFit
+# strings are upstream's (k8s v1.24 fit.go InsufficientResource.Reason, not vendored: unpinned); the rest are the
+# koordinator plugins' own (nodenumaresource/plugin.go:50-55, resource_manager.go:258,450, topology_hint.go:36,
+# reservation/plugin.go:50,58).  Slots that collapse several reference strings say so in DESIGN.md 4.9.2.
+REASON_TEXT = {
+    abi.REASON_STATIC: REASON_OF_BIT[abi.ST_STATIC_FAIL],
+    abi.REASON_FIT_PODS: "Too many pods",
+    abi.REASON_FIT_CPU: "Insufficient cpu",
+    abi.REASON_FIT_MEM: "Insufficient memory",
+    abi.REASON_FIT_EPH: "Insufficient ephemeral-storage",
+    abi.REASON_FIT_BCPU: "Insufficient kubernetes.io/batch-cpu",
+    abi.REASON_FIT_BMEM: "Insufficient kubernetes.io/batch-memory",
+    abi.REASON_LA_USAGE: REASON_OF_BIT[abi.ST_LA_FAIL],       # load_aware.go:45-46 without the resource name
+    abi.REASON_NUMA_POD_ERROR: "the requested CPUs must be integer",
+    abi.REASON_NUMA_AMP_CPU: "Insufficient amplified cpu",
+    abi.REASON_NUMA_NO_TOPOLOGY: "node(s) CPU Topology not found",
+    abi.REASON_NUMA_SMT_ALIGN: "node(s) requested cpus not multiple cpus per core",
+    abi.REASON_NUMA_FULL_PCPUS_ONLY: "node(s) required FullPCPUs policy",
+    abi.REASON_NUMA_CPUS: "not enough cpus available to satisfy request",
+    abi.REASON_NUMA_REQUIRED_POLICY: "insufficient CPUs to satisfy required cpu bind policy",
+    abi.REASON_NUMA_NO_ZONES: "node(s) missing NUMA resources",
+    abi.REASON_NUMA_POLICY: "node(s) NUMA Topology affinity error",
+    abi.REASON_RESV_AFFINITY: "node(s) no reservations match reservation affinity",
+    abi.REASON_RESV_INSUFFICIENT: "node(s) reservations insufficient resources",
+}
+assert sorted(REASON_TEXT) == list(range(abi.REASON_COUNT))
+
+
+def fit_error_message(rec, n: int) -> str:
+    """Upstream FitError.Error() (k8s v1.24 framework/types.go, not vendored:
+    unpinned) over a koordhip_reasons record: '0/N nodes are available: ' + the
+    '<count> <reason>' strings of `first`, sorted as strings, joined with ', ',
+    then '.'.  A node that fails NodeResourcesFit on several resources counts
+    under each, as upstream's per-reason histogram does."""
+    parts = sorted(f"{int(rec['first'][r])} {REASON_TEXT[r]}" for r in range(abi.REASON_COUNT)
+                   if int(rec["first"][r]) > 0)
+    return f"0/{int(n)} nodes are available: " + ", ".join(parts) + "."
+
+
+def preemption_might_help(rec, n: int) -> bool:
+    """Whether nodesWherePreemptionMightHelp leaves PostFilter any node: some
+    failing node's status is not UnschedulableAndUnresolvable."""
+    return int(n) - int(rec["feasible"]) - int(rec["unresolvable"]) > 0
+
+
 def _slot(bit: int) -> int:
     return bit.bit_length() - 1
 

@@ -296,6 +296,39 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_fetch_node_status(self._ctx, int(pod_index), abi.ptr(out, C.c_uint8)))
         return out
 
+    # ---- ... and the FitError reasons per node (abi.REASON_*; diagnosis.fit_error_message reads the records)
+    def diagnose_reasons(self, pods: np.ndarray) -> np.ndarray:
+        """Per-reason node counts (abi.REASONS_DTYPE records) of `pods` against
+        the current state; diagnose()'s envelope, stateless, no commit."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        out = np.zeros(len(pods), abi.REASONS_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_diagnose_reasons(self._ctx, pods.ctypes.data, len(pods), out.ctypes.data))
+        return out
+
+    def node_reasons(self, pod) -> np.ndarray:
+        """[n] 32-bit abi.REASON_* masks of one pod against the current state:
+        the reasons of every failing plugin on each node."""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        if len(pod) != 1:
+            raise ValueError("node_reasons takes one pod")
+        out = np.zeros(self.n, np.uint32)
+        abi.check(self.lib, self.lib.koordhip_node_reasons(self._ctx, pod.ctypes.data, abi.ptr(out, C.c_uint32)))
+        return out
+
+    def fetch_reasons(self, n: int) -> np.ndarray:
+        """fetch_diagnosis() with reason records: the last place call's unplaced
+        pods at their decision states; all-zero records for placed pods."""
+        out = np.zeros(n, abi.REASONS_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_fetch_reasons(self._ctx, out.ctypes.data, n))
+        return out
+
+    def fetch_node_reasons(self, pod_index: int) -> np.ndarray:
+        """fetch_node_status() with reason masks: [n] abi.REASON_* masks of one
+        unplaced pod of the last place call at its decision state."""
+        out = np.zeros(self.n, np.uint32)
+        abi.check(self.lib, self.lib.koordhip_fetch_node_reasons(self._ctx, int(pod_index), abi.ptr(out, C.c_uint32)))
+        return out
+
     # ---- preemption dry run (koordinator_amd.preemption builds the records)
     def preempt_load_pods(self, assigned: np.ndarray, pdb_allowed=()):
         """Upload the table of the pods that sit on the nodes (abi.ASSIGNED_DTYPE)
