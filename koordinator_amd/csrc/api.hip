@@ -3061,7 +3061,7 @@ int print_stamps(koordhip_ctx *c, const kh::PlacePlan &plan) {
                  q[11] / nc, q[12] / nc);
   }
   {
-    uint64_t q[4] = {0, 0, 0, 0}, rw[7] = {0, 0, 0, 0, 0, 0, 0};
+    uint64_t q[4] = {0, 0, 0, 0}, rw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     HIP_TRY(hipMemcpy(q, c->d_dbg + 90, sizeof(q), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rw, c->d_dbg + 107, sizeof(rw), hipMemcpyDeviceToHost));
     std::fprintf(stderr, "[koordhip stamps] chain re-walks: walk + keys %llu (entries + claims %llu, row + evaluation "
@@ -3069,9 +3069,10 @@ int print_stamps(koordhip_ctx *c, const kh::PlacePlan &plan) {
                  (unsigned long long)rw[5], (unsigned long long)rw[6], (unsigned long long)rw[1],
                  (unsigned long long)rw[2]);
     std::fprintf(stderr, "[koordhip stamps] chained decisions: %llu cycles, %llu pods resolved | claim tables %llu  "
-                 "re-walks %llu  re-check + closure %llu  final table %llu\n", (unsigned long long)h[62],
+                 "re-walks %llu  re-check + closure %llu  final table %llu | rounds with a lazy "
+                 "claim table %llu\n", (unsigned long long)h[62],
                  (unsigned long long)h[63], (unsigned long long)q[0], (unsigned long long)q[1],
-                 (unsigned long long)q[2], (unsigned long long)q[3]);
+                 (unsigned long long)q[2], (unsigned long long)q[3], (unsigned long long)rw[7]);
   }
   if (plan.ext_pipe) {
     uint64_t q[8];

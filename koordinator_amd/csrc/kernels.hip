@@ -2066,6 +2066,7 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   uint64_t c_chain = 0;                              // chained decisions: cycles (pods resolved: dbg[63])
   uint64_t c_ch[4] = {0, 0, 0, 0};                   // ... split: claim tables, re-walks, re-check + closure, final table
   uint64_t c_rw[4] = {0, 0, 0, 0}, n_chbm = 0;             // ... re-walks: walk + keys, winners' rows; chain HBM row loads
+  uint64_t n_lazy = 0;                               // rounds whose final claim table was built (by the loop's first claimer())
   uint64_t c_ext = 0, n_ext = 0;                     // device pods: cycles from the hand-off to the worker's answer, pods
   // ---- a round's global reads: lists -> LDS (stride kp, zero padded), pod
   //      records, and the rows of each pod's first HP list entries (slot HP j + q)
@@ -2393,33 +2394,43 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       //      entries, stays on the general path.  Each pass re-checks the valid
       //      pods against the valid claims and closes the dependencies in pod
       //      order; up to RES_CHAIN_PASSES passes, eight pods per lane group.
+      //      The claim table of the final valid pods has one reader, the loop's
+      //      claimer() on the general path of a monotone pod with X entries above
+      //      its c -- config 4: 1,420 of 4,167 rounds have one.  The loop builds
+      //      it there, at the round's first such pod (claims_stale), not here
+      //      (-DKH_CHAIN_EAGER_CLAIMS: after the last pass, every round).  Until
+      //      then ckey / cval keep the last pass's table; nothing else reads
+      //      them (the helper waves read dec_*), and the end-of-round clear the
+      //      next prologue's inserts need stays where it is.
+      auto wsync = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      };
+      // ckey / cval lack the claims of the pods the last pass resolved
+      bool claims_stale = false;
+      // the claims of the valid (dec_c == 0) pods: staged winner -> first pod
+      auto claims = [&]() {
+        for (int32_t x = lane; x < RES_HASH; x += 64) {
+          ckey[x] = -1;
+          cval[x] = 64;
+        }
+        wsync();
+        if (lane < n_pods && dec_c[lane] == 0 && dec_key[lane] != 0ull) {
+          const int32_t sw2 = key_node(dec_key[lane]);
+          uint32_t h = res_hash(sw2);
+          for (;;) {
+            const int32_t prev = atomicCAS(&ckey[h], -1, sw2);
+            if (prev == -1 || prev == sw2) {
+              atomicMin(&cval[h], lane);
+              break;
+            }
+            h = (h + 1) & (RES_HASH - 1);
+          }
+        }
+        wsync();
+      };
       if (chain_on) {
         const uint64_t t_c0 = dbg ? stamp() : 0;
-        auto wsync = [&]() {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        };
-        // the claims of the valid (dec_c == 0) pods: staged winner -> first pod
-        auto claims = [&]() {
-          for (int32_t x = lane; x < RES_HASH; x += 64) {
-            ckey[x] = -1;
-            cval[x] = 64;
-          }
-          wsync();
-          if (lane < n_pods && dec_c[lane] == 0 && dec_key[lane] != 0ull) {
-            const int32_t sw2 = key_node(dec_key[lane]);
-            uint32_t h = res_hash(sw2);
-            for (;;) {
-              const int32_t prev = atomicCAS(&ckey[h], -1, sw2);
-              if (prev == -1 || prev == sw2) {
-                atomicMin(&cval[h], lane);
-                break;
-              }
-              h = (h + 1) & (RES_HASH - 1);
-            }
-          }
-          wsync();
-        };
         auto claimer_of = [&](int32_t y) -> int32_t {
           uint32_t q = res_hash(y);
           for (;;) {
@@ -2617,7 +2628,11 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
           fresh = false;  // (the resolved pods' new claims are not in the table)
           clap(2);
         }
+#ifdef KH_CHAIN_EAGER_CLAIMS
         if (!fresh) claims();  // the loop's claimer(): the valid pods' winners
+#else
+        claims_stale = !fresh;  // the loop's claimer() builds the table when a pod first probes it
+#endif
         clap(3);
         if (lane == 0) __hip_atomic_store(&sh_chain, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (dbg) c_chain += stamp() - t_c0;
@@ -2812,6 +2827,11 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
             const uint64_t e = h ? e1 : e0;
             const bool xh = (h ? x1 : x0) && 64 * h + lane < first;
             if (__ballot(xh)) {
+              if (claims_stale) {  // claimer()'s first probe since the chained decisions (wave-uniform)
+                claims();
+                claims_stale = false;
+                if (dbg) n_lazy++;
+              }
               uint64_t kv = 0;
               if (xh) {
                 const int32_t y = key_node(e);
@@ -3288,6 +3308,7 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
     atomicAdd((unsigned long long *)&dbg[109], (unsigned long long)n_chbm);
     atomicAdd((unsigned long long *)&dbg[112], (unsigned long long)c_rw[2]);
     atomicAdd((unsigned long long *)&dbg[113], (unsigned long long)c_rw[3]);
+    atomicAdd((unsigned long long *)&dbg[114], (unsigned long long)n_lazy);
     atomicAdd((unsigned long long *)&dbg[30], (unsigned long long)c_ext);
     atomicAdd((unsigned long long *)&dbg[31], (unsigned long long)n_ext);
   }

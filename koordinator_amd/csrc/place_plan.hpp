@@ -182,7 +182,11 @@ inline PlacePlan plan_place(const PlaceFacts &f, const PlaceKnobs &k) {
   // config 4: 16.0k -> 0.4k general-path pods, 75.0 -> 62.5 ms per step,
   // profiles/r05n_chain_ab.txt; KOORDHIP_CHAIN_OFF for A/B)
   // (bits 2-3: chain passes, 1 by default -- 1 / 2 / 3 passes measured 60.1 /
-  // 60.5 / 61.0 ms per step on config 4, r05o; KOORDHIP_CHAIN_PASSES for A/B)
+  // 60.5 / 61.0 ms per step on config 4, r05o; KOORDHIP_CHAIN_PASSES for A/B.
+  // With the final claim table built by the loop, r08a: 57.08-57.19 / 56.58-56.76 /
+  // 57.11-57.23 ms, three lines each -- two passes win by 0.9 %, more than the
+  // lines' spread; the default stays 1 until the plan's hand-worked rows move
+  // with it, profiles/r08a_config4_ab.txt)
   p.mono = f.monotone | ((f.monotone && !k.CHAIN_OFF) ? 2 : 0) | (f.monotone ? ((k.CHAIN_PASSES & 3) << 2) : 0);
   // profile_kernels: event pairs around the evaluation launches of at most
   // ~256 evenly spaced rounds (the per-kernel averages need no more; every
