@@ -3379,40 +3379,83 @@ int koordhip_uncommit(koordhip_ctx *c, const koordhip_pod *pod, int32_t node, co
   return commit_impl(c, pod, node, -1, const_cast<uint64_t *>(cpus));
 }
 
-// ---- unschedulable-pod diagnosis (diag.hip) --------------------------------
+}  // extern "C"
 
-int koordhip_diagnose(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_pods, koordhip_diag *out) {
+// ---- unschedulable-pod diagnosis (diag.hip, reasons.hip) --------------------
+// Two kinds of answer, one host path per call shape: per-plugin koordhip_diag
+// records / status bytes, and per-reason koordhip_reasons records / 32-bit
+// reason masks.  A kind names the record, a node's value in the one-pod plane
+// and the two launch wrappers; the calls share their checks, workspaces and
+// error codes.
+namespace {
+
+struct StatusKind {
+  using Rec = koordhip_diag;
+  using Plane = uint8_t;
+  static constexpr auto current = kh::launch_diag;
+  static constexpr auto replay = kh::launch_diag_replay;
   static_assert(sizeof(koordhip_diag) == 136, "koordhip_diag is 34 int32 counters");
-  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+};
+struct ReasonKind {
+  using Rec = koordhip_reasons;
+  using Plane = uint32_t;
+  static constexpr auto current = kh::launch_reasons;
+  static constexpr auto replay = kh::launch_reasons_replay;
+  static_assert(sizeof(koordhip_reasons) == 264, "koordhip_reasons is 66 int32 counters");
+};
+
+// the pods of a current-state call into the context's workspace
+int diag_upload_pods(koordhip_ctx *c, const std::vector<kh::DevPod> &hp) {
+  const size_t pb = hp.size() * sizeof(kh::DevPod);
+  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, pb)) return e;
+  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), pb, hipMemcpyHostToDevice, c->stream));
+  return 0;
+}
+
+// How every record-producing call ends: rb zeroed bytes of d_diag_rec for
+// `launch` to count into, copied to dst; the stream drained.
+template <class Launch>
+int diag_rec_run(koordhip_ctx *c, size_t rb, void *dst, Launch launch) {
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
+  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
+  HIP_TRY(launch());
+  HIP_TRY(hipMemcpyAsync(dst, c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// The current state: n_pods records into `out`, or with `plane` one pod's [n]
+// values.  `who`: the calling function, for the texts that name it.
+template <class K>
+int diag_current(koordhip_ctx *c, const char *who, const koordhip_pod *pods, int32_t n_pods, typename K::Rec *out,
+                 typename K::Plane *plane) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
   if (n_pods == 0) return 0;
   bool reserve = false;
   if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
   if (c->seq)
-    return fail(KOORDHIP_EINVAL, "koordhip_diagnose: the profile / snapshot evaluates in the sequential cycle "
+    return fail(KOORDHIP_EINVAL, std::string(who) + ": the profile / snapshot evaluates in the sequential cycle "
                                  "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
-  if (reserve) return fail(KOORDHIP_EINVAL, "koordhip_diagnose: reserve / reservation-operating-mode pods are not covered");
+  if (reserve) return fail(KOORDHIP_EINVAL, std::string(who) + ": reserve / reservation-operating-mode pods are not covered");
   std::vector<kh::DevPod> hp;
   if (int e = to_dev_pods(pods, n_pods, hp)) return e;
   HIP_TRY(hipSetDevice(c->device));
-  const size_t rb = (size_t)n_pods * sizeof(koordhip_diag);
-  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, (size_t)n_pods * sizeof(kh::DevPod))) return e;
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
-  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), (size_t)n_pods * sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
-  HIP_TRY(kh::launch_diag(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods), n_pods,
-                          static_cast<int32_t *>(c->d_diag_rec), c->stream));
-  HIP_TRY(hipMemcpyAsync(out, c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  const size_t rb = plane ? (size_t)c->n * sizeof(typename K::Plane) : (size_t)n_pods * sizeof(typename K::Rec);
+  if (rb == 0) return 0;
+  if (int e = diag_upload_pods(c, hp)) return e;
+  return diag_rec_run(c, rb, plane ? static_cast<void *>(plane) : static_cast<void *>(out), [&] {
+    return K::current(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods), n_pods,
+                      plane ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
+                      plane ? static_cast<typename K::Plane *>(c->d_diag_rec) : nullptr, c->stream);
+  });
 }
 
-// The checks koordhip_fetch_diagnosis and koordhip_fetch_node_status share:
-// the last place call drained, nothing changed the state since, and the call
-// lies in the envelope where every commit of the stream is invertible from
-// what the engine keeps (koordhip_uncommit's).
-static int diag_replay_ready(koordhip_ctx *c) {
+// The checks the decision-state calls share: the last place call drained,
+// nothing changed the state since, and the call lies in the envelope where
+// every commit of the stream is invertible from what the engine keeps
+// (koordhip_uncommit's).
+int diag_replay_ready(koordhip_ctx *c) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3435,8 +3478,11 @@ static int diag_replay_ready(koordhip_ctx *c) {
   return 0;
 }
 
-int koordhip_fetch_diagnosis(koordhip_ctx *c, koordhip_diag *out, int32_t n_pods) {
-  if (!c || (!out && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+// The decision states: the records of the unplaced pods among the first n_pods
+// of the last place call; every other record zero.
+template <class K>
+int diag_fetch_records(koordhip_ctx *c, typename K::Rec *out, int32_t n_pods) {
+  using Rec = typename K::Rec;
   if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
   if (int e = diag_replay_ready(c)) return e;
   if (n_pods > c->n_staged) return fail(KOORDHIP_EINVAL, "n_pods exceeds the staged stream");
@@ -3450,25 +3496,24 @@ int koordhip_fetch_diagnosis(koordhip_ctx *c, koordhip_diag *out, int32_t n_pods
   int32_t U = 0;
   HIP_TRY(hipMemcpyAsync(&U, l.tot + 1, sizeof(U), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_diag));
+  std::memset(out, 0, (size_t)n_pods * sizeof(Rec));
   if (U <= 0) return 0;
-  const size_t rb = (size_t)U * sizeof(koordhip_diag);
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
-  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
-  HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, l, U, -1, static_cast<int32_t *>(c->d_diag_rec),
-                                 nullptr, c->stream));
-  std::vector<koordhip_diag> rec((size_t)U);
+  std::vector<Rec> rec((size_t)U);
   std::vector<int32_t> ul((size_t)U);
-  HIP_TRY(hipMemcpyAsync(rec.data(), c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(ul.data(), l.ul, (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  if (int e = diag_rec_run(c, (size_t)U * sizeof(Rec), rec.data(), [&] {
+        return K::replay(c->dc, c->d, c->d_pods, c->d_cpus, l, U, -1, static_cast<int32_t *>(c->d_diag_rec), nullptr,
+                         c->stream);
+      }))
+    return e;
   for (int32_t k = 0; k < U; k++)
     if (ul[k] >= 0 && ul[k] < n_pods) out[ul[k]] = rec[k];
   return 0;
 }
 
-int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *status) {
-  if (!c || !status) return fail(KOORDHIP_EINVAL, "NULL argument");
+// ... and the [n] values of one unplaced pod of it.
+template <class K>
+int diag_fetch_plane(koordhip_ctx *c, int32_t pod_index, typename K::Plane *plane) {
   if (int e = diag_replay_ready(c)) return e;
   if (pod_index < 0 || pod_index >= c->n_staged) return fail(KOORDHIP_EINVAL, "pod_index outside the staged stream");
   int32_t node = 0;
@@ -3476,114 +3521,55 @@ int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *stat
   if (node >= 0) return fail(KOORDHIP_EINVAL, "the pod was placed: it has no unschedulable status");
   const int32_t P = c->n_staged, n = c->n;
   if (n == 0) return 0;
+  const size_t rb = (size_t)n * sizeof(typename K::Plane);
   if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, (size_t)n)) return e;
+  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
   int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
   HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
-  HIP_TRY(kh::launch_diag_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
-                                 static_cast<uint8_t *>(c->d_diag_rec), c->stream));
-  HIP_TRY(hipMemcpyAsync(status, c->d_diag_rec, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(K::replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
+                    static_cast<typename K::Plane *>(c->d_diag_rec), c->stream));
+  HIP_TRY(hipMemcpyAsync(plane, c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
 
-// ---- FitError reasons (reasons.hip) ------------------------------------------
-// The four calls mirror koordhip_diagnose, koordhip_fetch_diagnosis and
-// koordhip_fetch_node_status: their checks, workspaces and error codes, with
-// koordhip_reasons records / 32-bit reason masks in place of koordhip_diag
-// records / status bytes.
+}  // namespace
 
-static int reasons_current(koordhip_ctx *c, const char *who, const koordhip_pod *pods, int32_t n_pods,
-                           koordhip_reasons *out, uint32_t *mask) {
-  static_assert(sizeof(koordhip_reasons) == 264, "koordhip_reasons is 66 int32 counters");
-  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
-  bool reserve = false;
-  if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
-  if (c->seq)
-    return fail(KOORDHIP_EINVAL, std::string(who) + ": the profile / snapshot evaluates in the sequential cycle "
-                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
-  if (reserve) return fail(KOORDHIP_EINVAL, std::string(who) + ": reserve / reservation-operating-mode pods are not covered");
-  std::vector<kh::DevPod> hp;
-  if (int e = to_dev_pods(pods, n_pods, hp)) return e;
-  HIP_TRY(hipSetDevice(c->device));
-  const size_t rb = mask ? (size_t)c->n * sizeof(uint32_t) : (size_t)n_pods * sizeof(koordhip_reasons);
-  if (rb == 0) return 0;
-  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, (size_t)n_pods * sizeof(kh::DevPod))) return e;
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
-  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), (size_t)n_pods * sizeof(kh::DevPod), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
-  HIP_TRY(kh::launch_reasons(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods), n_pods,
-                             mask ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
-                             mask ? static_cast<uint32_t *>(c->d_diag_rec) : nullptr, c->stream));
-  HIP_TRY(hipMemcpyAsync(mask ? static_cast<void *>(mask) : static_cast<void *>(out), c->d_diag_rec, rb,
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+extern "C" {
+
+int koordhip_diagnose(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_pods, koordhip_diag *out) {
+  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diag_current<StatusKind>(c, "koordhip_diagnose", pods, n_pods, out, nullptr);
 }
 
 int koordhip_diagnose_reasons(koordhip_ctx *c, const koordhip_pod *pods, int32_t n_pods, koordhip_reasons *out) {
   if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
-  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
-  if (n_pods == 0) return 0;
-  return reasons_current(c, "koordhip_diagnose_reasons", pods, n_pods, out, nullptr);
+  return diag_current<ReasonKind>(c, "koordhip_diagnose_reasons", pods, n_pods, out, nullptr);
 }
 
 int koordhip_node_reasons(koordhip_ctx *c, const koordhip_pod *pod, uint32_t *mask) {
   if (!c || !pod || !mask) return fail(KOORDHIP_EINVAL, "NULL argument");
-  return reasons_current(c, "koordhip_node_reasons", pod, 1, nullptr, mask);
+  return diag_current<ReasonKind>(c, "koordhip_node_reasons", pod, 1, nullptr, mask);
+}
+
+int koordhip_fetch_diagnosis(koordhip_ctx *c, koordhip_diag *out, int32_t n_pods) {
+  if (!c || (!out && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diag_fetch_records<StatusKind>(c, out, n_pods);
 }
 
 int koordhip_fetch_reasons(koordhip_ctx *c, koordhip_reasons *out, int32_t n_pods) {
   if (!c || (!out && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
-  if (int e = diag_replay_ready(c)) return e;
-  if (n_pods > c->n_staged) return fail(KOORDHIP_EINVAL, "n_pods exceeds the staged stream");
-  if (n_pods == 0) return 0;
-  // the lists cover the whole stream: the commits of pods >= n_pods are un-applied too
-  const int32_t P = c->n_staged, n = c->n;
-  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
-  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
-  const kh::DiagLists l = kh::diag_lists(ws, n, P);
-  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
-  int32_t U = 0;
-  HIP_TRY(hipMemcpyAsync(&U, l.tot + 1, sizeof(U), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_reasons));
-  if (U <= 0) return 0;
-  const size_t rb = (size_t)U * sizeof(koordhip_reasons);
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
-  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
-  HIP_TRY(kh::launch_reasons_replay(c->dc, c->d, c->d_pods, c->d_cpus, l, U, -1, static_cast<int32_t *>(c->d_diag_rec),
-                                    nullptr, c->stream));
-  std::vector<koordhip_reasons> rec((size_t)U);
-  std::vector<int32_t> ul((size_t)U);
-  HIP_TRY(hipMemcpyAsync(rec.data(), c->d_diag_rec, rb, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(ul.data(), l.ul, (size_t)U * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  for (int32_t k = 0; k < U; k++)
-    if (ul[k] >= 0 && ul[k] < n_pods) out[ul[k]] = rec[k];
-  return 0;
+  return diag_fetch_records<ReasonKind>(c, out, n_pods);
+}
+
+int koordhip_fetch_node_status(koordhip_ctx *c, int32_t pod_index, uint8_t *status) {
+  if (!c || !status) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diag_fetch_plane<StatusKind>(c, pod_index, status);
 }
 
 int koordhip_fetch_node_reasons(koordhip_ctx *c, int32_t pod_index, uint32_t *mask) {
   if (!c || !mask) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (int e = diag_replay_ready(c)) return e;
-  if (pod_index < 0 || pod_index >= c->n_staged) return fail(KOORDHIP_EINVAL, "pod_index outside the staged stream");
-  int32_t node = 0;
-  HIP_TRY(hipMemcpy(&node, c->d_out + pod_index, sizeof(node), hipMemcpyDeviceToHost));
-  if (node >= 0) return fail(KOORDHIP_EINVAL, "the pod was placed: it has no unschedulable status");
-  const int32_t P = c->n_staged, n = c->n;
-  if (n == 0) return 0;
-  if (int e = ensure(c, &c->d_diag_ws, &c->diag_ws_cap, kh::diag_ws_ints(n, P) * sizeof(int32_t))) return e;
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, (size_t)n * sizeof(uint32_t))) return e;
-  int32_t *ws = static_cast<int32_t *>(c->d_diag_ws);
-  HIP_TRY(kh::launch_diag_lists(ws, c->d_out, P, n, c->stream));
-  HIP_TRY(kh::launch_reasons_replay(c->dc, c->d, c->d_pods, c->d_cpus, kh::diag_lists(ws, n, P), 1, pod_index, nullptr,
-                                    static_cast<uint32_t *>(c->d_diag_rec), c->stream));
-  HIP_TRY(hipMemcpyAsync(mask, c->d_diag_rec, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return diag_fetch_plane<ReasonKind>(c, pod_index, mask);
 }
 
 // ---- ... for every profile koordhip_eval_ext evaluates (diag_ext.hip) -------
@@ -3623,25 +3609,20 @@ static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const ko
     if (out) std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_diag));
     return 0;
   }
-  const size_t pb = (size_t)n_pods * sizeof(kh::DevPod), xb = (size_t)n_pods * sizeof(kh::DevPodX);
+  const size_t xb = (size_t)n_pods * sizeof(kh::DevPodX);
   const size_t rb = status ? (size_t)n * sizeof(uint16_t) : (size_t)n_pods * sizeof(koordhip_diag);
-  if (int e = ensure(c, &c->d_diag_pods, &c->diag_pods_cap, pb)) return e;
   if (ext)
     if (int e = ensure(c, &c->d_diagx_podx, &c->diagx_podx_cap, xb)) return e;
   if (int e = ensure(c, &c->d_diagx_ws, &c->diagx_ws_cap, kh::diag_ext_ws_bytes(n_pods))) return e;
-  if (int e = ensure(c, &c->d_diag_rec, &c->diag_rec_cap, rb)) return e;
-  HIP_TRY(hipMemcpyAsync(c->d_diag_pods, hp.data(), pb, hipMemcpyHostToDevice, c->stream));
+  if (int e = diag_upload_pods(c, hp)) return e;
   if (ext) HIP_TRY(hipMemcpyAsync(c->d_diagx_podx, ext, xb, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipMemsetAsync(c->d_diag_rec, 0, rb, c->stream));
   const int32_t rs = (c->dc.resv && (c->cfg.score_plugins & KOORDHIP_PLUGIN_RESERVATION)) ? 1 : 0;
-  HIP_TRY(kh::launch_diag_ext(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods),
-                              ext ? static_cast<const kh::DevPodX *>(c->d_diagx_podx) : nullptr, n_pods, rs, c->pts, c->ipa,
-                              c->d_diagx_ws, hhost, status ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
-                              status ? static_cast<uint16_t *>(c->d_diag_rec) : nullptr, c->stream));
-  HIP_TRY(hipMemcpyAsync(status ? static_cast<void *>(status) : static_cast<void *>(out), c->d_diag_rec, rb,
-                         hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return 0;
+  return diag_rec_run(c, rb, status ? static_cast<void *>(status) : static_cast<void *>(out), [&] {
+    return kh::launch_diag_ext(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods),
+                               ext ? static_cast<const kh::DevPodX *>(c->d_diagx_podx) : nullptr, n_pods, rs, c->pts,
+                               c->ipa, c->d_diagx_ws, hhost, status ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
+                               status ? static_cast<uint16_t *>(c->d_diag_rec) : nullptr, c->stream);
+  });
 }
 
 int koordhip_diagnose_ext(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,

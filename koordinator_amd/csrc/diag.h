@@ -9,9 +9,11 @@ namespace kh {
 
 constexpr int kDiagWords = (int)(sizeof(koordhip_diag) / sizeof(int32_t));  // a record as int32 counters
 
-// k_diag: out[p] += the record of pods[p] on the current state (out zeroed by the caller).
+// k_diag_current with the status kind: out[p] += the record of pods[p] on the
+// current state (out zeroed by the caller).  With `status` (n_pods == 1): node
+// i's status byte instead.
 hipError_t launch_diag(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t *out,
-                       hipStream_t s);
+                       uint8_t *status, hipStream_t s);
 
 // The replay's lists, built on device from a place call's out_node [P] in one
 // int32 workspace of diag_ws_ints(n, P) words:

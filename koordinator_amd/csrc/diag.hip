@@ -1,21 +1,12 @@
 // diag.hip -- why a pod is unschedulable: per-plugin node counts of its Filter
 // result (koordhip_diag), reduced on device.
 //
-//   k_diag            stateless: pods against the current state.  256-node
-//                     tiles x pod tiles; a thread loads its node row once and
-//                     loops over the tile's pods (staged in LDS).  Per pod and
-//                     counter one ballot + popcount per wave, lane 0 adds into
-//                     an LDS table of whole records, the workgroup flushes its
-//                     non-zero entries with one atomic per counter (lanes on
-//                     consecutive words of a pod's record).
-//   k_diag_replay     (the template of diag_replay.hpp, here with the status
-//                     kind) the unplaced pods of the last place call at their
-//                     decision states, without a copy of the table: a commit
-//                     is exactly invertible (apply_delta / numa_apply with
-//                     sign -1, integers held in f64, order-independent), so a
-//                     thread loads its node's FINAL row, walks the unplaced
-//                     pods in descending order and, before it evaluates pod u,
-//                     un-applies its node's commits with a pod index > u.
+//   DiagStatus        the status kind of diag_kind.hpp's two kernels: the
+//                     KOORDHIP_ST_* bits of filter_status, counted per bit and
+//                     per first failing plugin.  k_diag_current with it answers
+//                     for pods against the current state, k_diag_replay for
+//                     the unplaced pods of the last place call at their
+//                     decision states.
 //   k_diag_mark / k_diag_scan / k_diag_fill / k_diag_sort
 //                     the replay's lists from the device-resident out_node:
 //                     per node its committed pods (count, exclusive scan,
@@ -26,23 +17,15 @@
 #include <algorithm>
 
 #include "diag.h"
-#include "diag_replay.hpp"
+#include "diag_kind.hpp"
 #include "eval.hpp"
 
 namespace kh {
 
-constexpr int DIAG_ANY = (int)(offsetof(koordhip_diag, any) / sizeof(int32_t));
-constexpr int DIAG_FIRST = (int)(offsetof(koordhip_diag, first) / sizeof(int32_t));
 constexpr int DIAG_NBITS = 5;               // the status bits these kernels produce: FIT, LA, NUMA, RESV, STATIC
 static_assert(offsetof(koordhip_diag, feasible) == 0 && kDiagWords == 2 + 2 * KOORDHIP_DIAG_BITS, "record layout");
 static_assert((KOORDHIP_ST_FIT_FAIL | KOORDHIP_ST_LA_FAIL | KOORDHIP_ST_NUMA_FAIL | KOORDHIP_ST_RESV_FAIL |
                KOORDHIP_ST_STATIC_FAIL) == (1u << DIAG_NBITS) - 1u, "the counted status bits are bits 0..4");
-
-// The first failing plugin in the framework's Filter order STATIC -> FIT -> LA
-// -> NUMA -> RESV (koordhip.h): the static bit, else the lowest set bit.
-__device__ __forceinline__ uint32_t first_fail(uint32_t st) {
-  return (st & KOORDHIP_ST_STATIC_FAIL) ? (uint32_t)KOORDHIP_ST_STATIC_FAIL : (st & (0u - st));
-}
 
 // the status bits the profile's Filter plugins can set (wave-uniform)
 __device__ __forceinline__ uint32_t status_bits(const DevCfg &c) {
@@ -53,83 +36,21 @@ __device__ __forceinline__ uint32_t status_bits(const DevCfg &c) {
          ((c.filt & KOORDHIP_PLUGIN_NODE_STATIC) ? KOORDHIP_ST_STATIC_FAIL : 0u);
 }
 
-// One wave's 64 nodes into a pod's LDS record.  Called by every lane of the
-// wave (the ballots are wave-wide); lanes that are not `live` count nowhere.
-__device__ __forceinline__ void diag_count(uint32_t st, bool live, uint32_t bits, int32_t *rec) {
-  const uint32_t f = first_fail(st);
-  const bool l0 = __lane_id() == 0;
-  const uint64_t ok = __ballot(live && st == 0u);
-  if (l0 && ok) atomicAdd(&rec[0], (int32_t)__popcll(ok));
-#pragma unroll
-  for (int b = 0; b < DIAG_NBITS; b++) {
-    if (!((bits >> b) & 1u)) continue;
-    const uint64_t ma = __ballot(live && ((st >> b) & 1u) != 0u);
-    const uint64_t mf = __ballot(live && f == (1u << b));
-    if (l0 && ma) atomicAdd(&rec[DIAG_ANY + b], (int32_t)__popcll(ma));
-    if (l0 && mf) atomicAdd(&rec[DIAG_FIRST + b], (int32_t)__popcll(mf));
-  }
-}
-
-// the replay's kind (diag_replay.hpp): the status bits into a koordhip_diag, or one pod's status bytes
+// the kind (diag_kind.hpp): the status bits into a koordhip_diag, or one pod's status bytes
 struct DiagStatus {
   static constexpr int WORDS = kDiagWords;
   using Plane = uint8_t;
   static __device__ __forceinline__ uint32_t slots(const DevCfg &c) { return status_bits(c); }
-  static __device__ __forceinline__ uint32_t eval(const DevCfg &c, const DevPod &pod, const NV &v, const NumaRowR &nr,
-                                                  const DevNumaClass *classes) {
-    return filter_status(c, pod, v, nr, classes, 0, 0u);
+  template <int S>
+  static __device__ __forceinline__ uint32_t eval(const DevCfg &c, const DevPod &pod, const NV &v,
+                                                  const NumaRowRS<S> &nr, const DevNumaClass *classes, int nmatch,
+                                                  uint32_t mm) {
+    return filter_status(c, pod, v, nr, classes, nmatch, mm);
   }
   static __device__ __forceinline__ void count(uint32_t st, bool live, uint32_t bits, int32_t *rec) {
-    diag_count(st, live, bits, rec);
+    status_count<DIAG_NBITS>(st, first_fail(st), live, bits, rec);
   }
 };
-
-// ---------------------------------------------------------------------------
-// k_diag: S = the reservation slots of the side row (1: no reservation columns)
-
-template <int S>
-__global__ __launch_bounds__(DIAG_THREADS) void k_diag(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
-                                                       int32_t n_pods, int32_t *__restrict__ out) {
-  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAG_PT * DIAG_POD_WORDS];
-  __shared__ int32_t tab[DIAG_PT * kDiagWords];
-  const int t = threadIdx.x;
-  const int32_t p0 = (int32_t)blockIdx.y * DIAG_PT;
-  const int32_t np = min(DIAG_PT, n_pods - p0);
-  const uint64_t *src = reinterpret_cast<const uint64_t *>(pods + p0);
-  for (int32_t w = t; w < np * DIAG_POD_WORDS; w += DIAG_THREADS) spw[w] = src[w];
-  for (int32_t w = t; w < np * kDiagWords; w += DIAG_THREADS) tab[w] = 0;
-  __syncthreads();
-  const DevPod *sp = reinterpret_cast<const DevPod *>(spw);
-  const int32_t i = (int32_t)blockIdx.x * DIAG_THREADS + t;
-  const bool live = i < d.n;
-  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
-  NumaRowRS<S> nr{};
-  load_numa<true>(nr, d, il, all);
-  if constexpr (S > 1) {
-    if (c.resv) {
-      load_resv(nr, d.rv, il);
-      // a topology-policy node's zone row shares the reserved CPUs' bytes (the Filter reads the zones only)
-      if (c.zones && topo_policy(nr.nflags) != 0) load_zones(nr, d, il);
-    }
-  }
-  const uint32_t bits = status_bits(c);
-  for (int32_t q = 0; q < np; q++) {
-    const DevPod pod = sp[q];
-    NV w = v;
-    int nmatch = 0;
-    uint32_t mm = 0;
-    if constexpr (S > 1) {
-      if (c.resv) nmatch = resv_restore(w, nr, pod, mm);  // the cycle's restore: every plugin sees the restored node
-    }
-    const uint32_t st = filter_status(c, pod, w, nr, d.nu.cls, nmatch, mm);
-    diag_count(st, live, bits, tab + q * kDiagWords);
-  }
-  __syncthreads();
-  diag_flush<kDiagWords>(tab, np, out + (size_t)p0 * kDiagWords);
-}
 
 // ---------------------------------------------------------------------------
 // the replay's lists
@@ -215,15 +136,8 @@ __global__ void k_diag_sort(const int32_t *__restrict__ off, int32_t *__restrict
 // host-side launch wrappers
 
 hipError_t launch_diag(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t *out,
-                       hipStream_t s) {
-  if (n_pods <= 0 || d.n <= 0) return hipSuccess;
-  const dim3 grid((d.n + DIAG_THREADS - 1) / DIAG_THREADS, (n_pods + DIAG_PT - 1) / DIAG_PT);
-  if (grid.y > 65535u) return hipErrorInvalidValue;
-  if (c.resv)
-    hipLaunchKernelGGL(k_diag<KOORDHIP_RESV_SLOTS_MAX>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, n_pods, out);
-  else
-    hipLaunchKernelGGL(k_diag<1>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, n_pods, out);
-  return hipGetLastError();
+                       uint8_t *status, hipStream_t s) {
+  return launch_current<DiagStatus>(c, d, pods, n_pods, out, status, s);
 }
 
 hipError_t launch_scan(const int32_t *in, int32_t *out, int32_t m, int32_t *total, hipStream_t s) {

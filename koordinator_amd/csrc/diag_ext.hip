@@ -20,11 +20,14 @@
 //                     (pts_prep: 256 threads and a barrier); the status is
 //                     filter_status on the restored row | seq_eval's bits |
 //                     pts_filter | ipa_filter, each the one definition the
-//                     cycle and koordhip_eval_ext use.  Counting is diag.hip's:
-//                     one ballot + popcount per wave and counter into an LDS
-//                     table of whole records, flushed with atomics on
-//                     consecutive words.  With a status pointer (one pod) the
-//                     node's 16-bit status is stored instead.
+//                     cycle and koordhip_eval_ext use.  The tile staging, the
+//                     row load, the counting (one ballot + popcount per wave
+//                     and counter into an LDS table of whole records) and the
+//                     flush are diag_kind.hpp's, shared with k_diag_current;
+//                     the kernel itself is not that template: it has its own
+//                     LDS, barriers inside the pod loop and another restore.
+//                     With a status pointer (one pod) the node's 16-bit status
+//                     is stored instead.
 //
 // None of this is cached across calls: every Reserve advances pts_cnt / ipa_cnt.
 #include <hip/hip_runtime.h>
@@ -33,58 +36,23 @@
 
 #include "diag.h"
 #include "diag_ext.h"
+#include "diag_kind.hpp"
 #include "seq.h"
 #include "seq_eval.hpp"
 
 namespace kh {
 
-constexpr int DIAGX_THREADS = 256;
-constexpr int DIAGX_POD_WORDS = (int)(sizeof(DevPod) / sizeof(uint64_t));
-constexpr int DIAGX_PODX_WORDS = (int)(sizeof(DevPodX) / sizeof(uint64_t));
-constexpr int DIAGX_ANY = (int)(offsetof(koordhip_diag, any) / sizeof(int32_t));
-constexpr int DIAGX_FIRST = (int)(offsetof(koordhip_diag, first) / sizeof(int32_t));
-constexpr int DIAGX_NBITS = 9;  // status bits 0..8: FIT, LA, NUMA, RESV, STATIC, DEVICE, XFIT, PTS, IPA
-static_assert(sizeof(DevPod) % sizeof(uint64_t) == 0 && sizeof(DevPodX) % sizeof(uint64_t) == 0,
-              "pod records are staged as 8-B words");
+constexpr int DIAGX_PODX_WORDS = tile_words<DevPodX>();
+static_assert(DIAGX_PT == DIAG_PT, "one pod tile for every diagnosis kernel");
 static_assert(offsetof(DevPodX, req) == 0 && DT >= 1 && DR == 3, "the empty record: req[0][0..2] = -1 are words 0..2");
-static_assert(KOORDHIP_ST_IPA_FAIL == 1u << (DIAGX_NBITS - 1), "the counted status bits are bits 0..8");
-static_assert(PK * 64 <= DIAGX_THREADS, "pts_prep: one wave per topology key");
-
-// The first failing plugin in the framework's Filter order (koordhip.h):
-// STATIC -> FIT -> XFIT -> PTS -> IPA -> LA -> NUMA -> DEVICE -> RESV.
-// Restricted to diag.hip's five bits it is that file's first_fail.
-__device__ __forceinline__ uint32_t first_fail_ext(uint32_t st) {
-  constexpr uint32_t order[DIAGX_NBITS] = {KOORDHIP_ST_STATIC_FAIL, KOORDHIP_ST_FIT_FAIL,    KOORDHIP_ST_XFIT_FAIL,
-                                           KOORDHIP_ST_PTS_FAIL,    KOORDHIP_ST_IPA_FAIL,    KOORDHIP_ST_LA_FAIL,
-                                           KOORDHIP_ST_NUMA_FAIL,   KOORDHIP_ST_DEVICE_FAIL, KOORDHIP_ST_RESV_FAIL};
-  uint32_t f = 0u;
-#pragma unroll
-  for (int k = DIAGX_NBITS - 1; k >= 0; k--) f = (st & order[k]) ? order[k] : f;
-  return f;
-}
-
-// One wave's 64 nodes into a pod's LDS record (diag.hip's diag_count over the
-// nine bits).  Called by every lane of the wave; lanes not `live` count nowhere.
-__device__ __forceinline__ void diag_count_ext(uint32_t st, bool live, int32_t *rec) {
-  const uint32_t f = first_fail_ext(st);
-  const bool l0 = __lane_id() == 0;
-  const uint64_t ok = __ballot(live && st == 0u);
-  if (l0 && ok) atomicAdd(&rec[0], (int32_t)__popcll(ok));
-#pragma unroll
-  for (int b = 0; b < DIAGX_NBITS; b++) {
-    const uint64_t ma = __ballot(live && ((st >> b) & 1u) != 0u);
-    const uint64_t mf = __ballot(live && f == (1u << b));
-    if (l0 && ma) atomicAdd(&rec[DIAGX_ANY + b], (int32_t)__popcll(ma));
-    if (l0 && mf) atomicAdd(&rec[DIAGX_FIRST + b], (int32_t)__popcll(mf));
-  }
-}
+static_assert(PK * 64 <= DIAG_THREADS, "pts_prep: one wave per topology key");
 
 // ---------------------------------------------------------------------------
 // the pre-passes
 
 // sums zeroed by the caller; one workgroup-local table per block, then one
 // global atomic per nonzero cell (the arithmetic of pts_init's fsum / fpres)
-__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_pts_sums(PtsArgs pa, int32_t n, PtsSums *__restrict__ sums,
+__global__ __launch_bounds__(DIAG_THREADS) void k_diag_pts_sums(PtsArgs pa, int32_t n, PtsSums *__restrict__ sums,
                                                                  int32_t *__restrict__ hmin, int32_t n_pods) {
   __shared__ PtsSums s;
   constexpr int NF = PC * PD, NP = PS * PK * 2;
@@ -93,8 +61,8 @@ __global__ __launch_bounds__(DIAGX_THREADS) void k_diag_pts_sums(PtsArgs pa, int
   const int t = threadIdx.x;
   const int32_t gid = (int32_t)(blockIdx.x * blockDim.x) + t, gsz = (int32_t)(gridDim.x * blockDim.x);
   for (int32_t p = gid; p < n_pods; p += gsz) hmin[p] = INT32_MAX;
-  for (int x = t; x < NF; x += DIAGX_THREADS) sf[x] = 0;
-  for (int x = t; x < NP; x += DIAGX_THREADS) sp[x] = 0u;
+  for (int x = t; x < NF; x += DIAG_THREADS) sf[x] = 0;
+  for (int x = t; x < NP; x += DIAG_THREADS) sp[x] = 0u;
   __syncthreads();
   for (int32_t i = gid; i < n; i += gsz) {
     const uint32_t el = pa.elig[i];
@@ -115,21 +83,21 @@ __global__ __launch_bounds__(DIAGX_THREADS) void k_diag_pts_sums(PtsArgs pa, int
     }
   }
   __syncthreads();
-  for (int x = t; x < NF; x += DIAGX_THREADS)
+  for (int x = t; x < NF; x += DIAG_THREADS)
     if (sf[x]) atomicAdd(&sums->fsum[0][0] + x, sf[x]);
-  for (int x = t; x < NP; x += DIAGX_THREADS)
+  for (int x = t; x < NP; x += DIAG_THREADS)
     if (sp[x]) atomicOr(&sums->fpres[0][0][0] + x, sp[x]);
 }
 
 // workgroup (p, y): pod p over the nodes y 256, (y + gridDim.y) 256, ...
-__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_hmin(PtsArgs pa, int32_t n, const DevPodX *__restrict__ podx,
+__global__ __launch_bounds__(DIAG_THREADS) void k_diag_hmin(PtsArgs pa, int32_t n, const DevPodX *__restrict__ podx,
                                                              int32_t *__restrict__ hmin) {
   const int32_t p = (int32_t)blockIdx.x;
   const PtsPod q = pts_pod(pa, podx[p]);
   if (!q.hhost) return;
   int32_t m = INT32_MAX;
-  for (int32_t i = (int32_t)blockIdx.y * DIAGX_THREADS + (int32_t)threadIdx.x; i < n;
-       i += (int32_t)gridDim.y * DIAGX_THREADS)
+  for (int32_t i = (int32_t)blockIdx.y * DIAG_THREADS + (int32_t)threadIdx.x; i < n;
+       i += (int32_t)gridDim.y * DIAG_THREADS)
     for (int k = 0; k < PK; k++)
       if (((q.hkeys & pa.host) >> k) & 1u) {
         const int32_t v = pts_host_match(pa, q, k, n, i);
@@ -143,55 +111,45 @@ __global__ __launch_bounds__(DIAGX_THREADS) void k_diag_hmin(PtsArgs pa, int32_t
 // k_diag_ext
 
 template <int SM>
-__global__ __launch_bounds__(DIAGX_THREADS) void k_diag_ext(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
+__global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
                                                             const DevPodX *__restrict__ podx, int32_t n_pods,
                                                             int32_t rs, PtsArgs pa, IpaArgs ia,
                                                             const PtsSums *__restrict__ psum,
                                                             const int32_t *__restrict__ hmin, int32_t *__restrict__ out,
                                                             uint16_t *__restrict__ status) {
   constexpr int S = SM >= 2 ? kSeqSlots<SM> : 1;  // the reservation slots of filter_status' side row
-  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAGX_PT * DIAGX_POD_WORDS];
-  __shared__ __attribute__((aligned(16))) uint64_t sxw[DIAGX_PT * DIAGX_PODX_WORDS];
-  __shared__ int32_t tab[DIAGX_PT * kDiagWords];
+  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAG_PT * tile_words<DevPod>()];
+  __shared__ __attribute__((aligned(16))) uint64_t sxw[DIAG_PT * DIAGX_PODX_WORDS];
+  __shared__ int32_t tab[DIAG_PT * kDiagWords];
   __shared__ PtsLds L;   // fsum / fpres from the call's sums; fmatch / fmin per pod (ssum: Score only, never read)
   __shared__ IpaLds IL;
   const int t = threadIdx.x;
-  const int32_t p0 = (int32_t)blockIdx.y * DIAGX_PT;
-  const int32_t np = min(DIAGX_PT, n_pods - p0);
-  const uint64_t *src = reinterpret_cast<const uint64_t *>(pods + p0);
-  for (int32_t w = t; w < np * DIAGX_POD_WORDS; w += DIAGX_THREADS) spw[w] = src[w];
+  const int32_t p0 = (int32_t)blockIdx.y * DIAG_PT;
+  const int32_t np = min(DIAG_PT, n_pods - p0);
+  stage_tile(spw, pods + p0, np);
   if (podx) {
-    const uint64_t *sx = reinterpret_cast<const uint64_t *>(podx + p0);
-    for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAGX_THREADS) sxw[w] = sx[w];
+    stage_tile(sxw, podx + p0, np);
   } else {  // the record of a pod without koordhip_pod_ext (no device request: gpu -1 = key absent)
-    for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAGX_THREADS) sxw[w] = (w % DIAGX_PODX_WORDS) < DR ? ~0ull : 0ull;
+    for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAG_THREADS) sxw[w] = (w % DIAGX_PODX_WORDS) < DR ? ~0ull : 0ull;
   }
-  for (int32_t w = t; w < np * kDiagWords; w += DIAGX_THREADS) tab[w] = 0;
+  for (int32_t w = t; w < np * kDiagWords; w += DIAG_THREADS) tab[w] = 0;
   const bool pts_on = pa.filt && pa.keys > 0;
   const bool ipa_on = ia.filt && ia.ents > 0;
   if (pts_on) {
-    for (int x = t; x < PC * PD; x += DIAGX_THREADS) (&L.fsum[0][0])[x] = (&psum->fsum[0][0])[x];
-    for (int x = t; x < PS * PK * 2; x += DIAGX_THREADS) (&L.fpres[0][0][0])[x] = (&psum->fpres[0][0][0])[x];
+    for (int x = t; x < PC * PD; x += DIAG_THREADS) (&L.fsum[0][0])[x] = (&psum->fsum[0][0])[x];
+    for (int x = t; x < PS * PK * 2; x += DIAG_THREADS) (&L.fpres[0][0][0])[x] = (&psum->fpres[0][0][0])[x];
   }
-  if (ipa_on) ipa_load(ia, IL, t, DIAGX_THREADS);
+  if (ipa_on) ipa_load(ia, IL, t, DIAG_THREADS);
   __syncthreads();
   const DevPod *sp = reinterpret_cast<const DevPod *>(spw);
   const DevPodX *sx = reinterpret_cast<const DevPodX *>(sxw);
-  const int32_t i = (int32_t)blockIdx.x * DIAGX_THREADS + t;
+  const int32_t i = (int32_t)blockIdx.x * DIAG_THREADS + t;
   const bool live = i < d.n;
   const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
   NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
   NumaRowRS<S> nr{};
-  load_numa<true>(nr, d, il, all);
-  if constexpr (S > 1) {
-    if (c.resv) {
-      load_resv(nr, d.rv, il);
-      // a topology-policy node's zone row shares the reserved CPUs' bytes (the Filter reads the zones only)
-      if (c.zones && topo_policy(nr.nflags) != 0) load_zones(nr, d, il);
-    }
-  }
+  load_filter_row(c, d, il, v, nr);
+  constexpr uint32_t bits = (1u << DIAG_STATUS_BITS) - 1u;  // every counter, whatever the profile
   for (int32_t q = 0; q < np; q++) {  // wave-uniform: the ballots and the barriers are valid
     const DevPod &pod = sp[q];
     const DevPodX &x = sx[q];
@@ -229,16 +187,12 @@ __global__ __launch_bounds__(DIAGX_THREADS) void k_diag_ext(DevCfg c, DevNodes d
     if (status) {
       if (live) status[i] = (uint16_t)st;
     } else {
-      diag_count_ext(st, live, tab + q * kDiagWords);
+      status_count<DIAG_STATUS_BITS>(st, first_fail(st), live, bits, tab + q * kDiagWords);
     }
     if (spread) __syncthreads();  // the next pod's pts_prep overwrites fmatch / fmin
   }
   __syncthreads();
-  if (!status)
-    for (int32_t w = t; w < np * kDiagWords; w += DIAGX_THREADS) {
-      const int32_t x = tab[w];
-      if (x) atomicAdd(&out[(size_t)p0 * kDiagWords + w], x);
-    }
+  if (!status) diag_flush<kDiagWords>(tab, np, out + (size_t)p0 * kDiagWords);
 }
 
 // ---------------------------------------------------------------------------
@@ -249,35 +203,35 @@ hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pod
                            uint16_t *status, hipStream_t s) {
   if (n_pods <= 0 || d.n <= 0) return hipSuccess;
   if ((status && n_pods != 1) || (!status && !out) || !ws) return hipErrorInvalidValue;
-  const dim3 grid((d.n + DIAGX_THREADS - 1) / DIAGX_THREADS, (n_pods + DIAGX_PT - 1) / DIAGX_PT);
+  const dim3 grid((d.n + DIAG_THREADS - 1) / DIAG_THREADS, (n_pods + DIAG_PT - 1) / DIAG_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
   PtsSums *psum = static_cast<PtsSums *>(ws);
   int32_t *hmin = reinterpret_cast<int32_t *>(psum + 1);
-  const int32_t nblk = std::min<int32_t>(1024, (d.n + DIAGX_THREADS - 1) / DIAGX_THREADS);
+  const int32_t nblk = std::min<int32_t>(1024, (d.n + DIAG_THREADS - 1) / DIAG_THREADS);
   if (ipa.filt)
     if (hipError_t e = launch_ipa_sums(ipa, d.n, s)) return e;
   if (pts.filt && pts.keys > 0) {
     if (hipError_t e = hipMemsetAsync(psum, 0, sizeof(PtsSums), s)) return e;
-    hipLaunchKernelGGL(k_diag_pts_sums, dim3(nblk), dim3(DIAGX_THREADS), 0, s, pts, d.n, psum, hmin, n_pods);
+    hipLaunchKernelGGL(k_diag_pts_sums, dim3(nblk), dim3(DIAG_THREADS), 0, s, pts, d.n, psum, hmin, n_pods);
     if (hhost && podx)
-      hipLaunchKernelGGL(k_diag_hmin, dim3(n_pods, std::min<int32_t>(64, nblk)), dim3(DIAGX_THREADS), 0, s, pts, d.n, podx,
+      hipLaunchKernelGGL(k_diag_hmin, dim3(n_pods, std::min<int32_t>(64, nblk)), dim3(DIAG_THREADS), 0, s, pts, d.n, podx,
                          hmin);
   }
   switch (seq_mode(c)) {
     case 3:
-      hipLaunchKernelGGL(k_diag_ext<3>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+      hipLaunchKernelGGL(k_diag_ext<3>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
                          out, status);
       break;
     case 2:
-      hipLaunchKernelGGL(k_diag_ext<2>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+      hipLaunchKernelGGL(k_diag_ext<2>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
                          out, status);
       break;
     case 1:
-      hipLaunchKernelGGL(k_diag_ext<1>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+      hipLaunchKernelGGL(k_diag_ext<1>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
                          out, status);
       break;
     default:
-      hipLaunchKernelGGL(k_diag_ext<0>, grid, dim3(DIAGX_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
+      hipLaunchKernelGGL(k_diag_ext<0>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
                          out, status);
   }
   return hipGetLastError();

@@ -10,8 +10,8 @@ namespace kh {
 
 constexpr int kReasonWords = (int)(sizeof(koordhip_reasons) / sizeof(int32_t));  // a record as int32 counters
 
-// k_reasons: out[p] += the record of pods[p] on the current state (out zeroed
-// by the caller).  With `mask` (n_pods == 1): node i's reason bits instead.
+// k_diag_current with the reason kind: launch_diag's arguments, records of
+// kReasonWords words, and with `mask` (n_pods == 1) node i's reason bits.
 hipError_t launch_reasons(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t *out,
                           uint32_t *mask, hipStream_t s);
 

@@ -3,20 +3,17 @@
 // and how many of the failing nodes are UnschedulableAndUnresolvable
 // (koordhip_reasons), reduced on device.
 //
-//   k_reasons         k_diag's shape: 256-node tiles x 32-pod tiles; a thread
-//                     loads its node row once and, per pod (staged in LDS),
-//                     restores on a copy and evaluates filter_reasons.  Per
-//                     counter one ballot + popcount per wave, lane 0 adds into
-//                     an LDS table of whole records (32 x 66 words), the
-//                     workgroup flushes its non-zero entries with atomics on
-//                     consecutive words.  The ballots of slots the profile
-//                     cannot produce are skipped.  With a mask pointer and one
-//                     pod: the node's 32 reason bits instead of a record.
-//   k_diag_replay     (diag_replay.hpp, here with the reason kind) the unplaced
-//                     pods of the last place call at their decision states.
+//   DiagReasons       the reason kind of diag_kind.hpp's two kernels: the
+//                     32 reason bits of filter_reasons into records of 66
+//                     words, with the unresolvable counter.  The ballots of
+//                     slots the profile cannot produce, and the first-ballot of
+//                     a reason no lane of the wave has, are skipped.
+//                     k_diag_current with it answers for pods against the
+//                     current state, k_diag_replay for the unplaced pods of
+//                     the last place call at their decision states.
 #include <hip/hip_runtime.h>
 
-#include "diag_replay.hpp"
+#include "diag_kind.hpp"
 #include "reasons.h"
 
 namespace kh {
@@ -77,66 +74,16 @@ __device__ __forceinline__ void reasons_count(uint32_t m, bool live, uint32_t sl
   }
 }
 
-// ---------------------------------------------------------------------------
-// k_reasons: S = the reservation slots of the side row (1: no reservation columns)
-
-template <int S>
-__global__ __launch_bounds__(DIAG_THREADS) void k_reasons(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
-                                                          int32_t n_pods, int32_t *__restrict__ out,
-                                                          uint32_t *__restrict__ mask) {
-  __shared__ __attribute__((aligned(16))) uint64_t spw[DIAG_PT * DIAG_POD_WORDS];
-  __shared__ int32_t tab[DIAG_PT * kReasonWords];
-  const int t = threadIdx.x;
-  const int32_t p0 = (int32_t)blockIdx.y * DIAG_PT;
-  const int32_t np = min(DIAG_PT, n_pods - p0);
-  const uint64_t *src = reinterpret_cast<const uint64_t *>(pods + p0);
-  for (int32_t w = t; w < np * DIAG_POD_WORDS; w += DIAG_THREADS) spw[w] = src[w];
-  for (int32_t w = t; w < np * kReasonWords; w += DIAG_THREADS) tab[w] = 0;
-  __syncthreads();
-  const DevPod *sp = reinterpret_cast<const DevPod *>(spw);
-  const int32_t i = (int32_t)blockIdx.x * DIAG_THREADS + t;
-  const bool live = i < d.n;
-  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
-  NumaRowRS<S> nr{};
-  load_numa<true>(nr, d, il, all);
-  if constexpr (S > 1) {
-    if (c.resv) {
-      load_resv(nr, d.rv, il);
-      // a topology-policy node's zone row shares the reserved CPUs' bytes (the Filter reads the zones only)
-      if (c.zones && topo_policy(nr.nflags) != 0) load_zones(nr, d, il);
-    }
-  }
-  const uint32_t slots = reason_slots(c);
-  for (int32_t q = 0; q < np; q++) {
-    const DevPod pod = sp[q];
-    NV w = v;
-    int nmatch = 0;
-    uint32_t mm = 0;
-    if constexpr (S > 1) {
-      if (c.resv) nmatch = resv_restore(w, nr, pod, mm);  // the cycle's restore: every plugin sees the restored node
-    }
-    const uint32_t m = filter_reasons(c, pod, w, nr, d.nu.cls, nmatch, mm);
-    if (mask) {
-      if (live) mask[i] = m;
-    } else {
-      reasons_count(m, live, slots, tab + q * kReasonWords);
-    }
-  }
-  __syncthreads();
-  if (!mask) diag_flush<kReasonWords>(tab, np, out + (size_t)p0 * kReasonWords);
-}
-
-// the replay's kind (diag_replay.hpp): the reason bits into a koordhip_reasons, or one pod's masks
+// the kind (diag_kind.hpp): the reason bits into a koordhip_reasons, or one pod's masks
 struct DiagReasons {
   static constexpr int WORDS = kReasonWords;
   using Plane = uint32_t;
   static __device__ __forceinline__ uint32_t slots(const DevCfg &c) { return reason_slots(c); }
-  static __device__ __forceinline__ uint32_t eval(const DevCfg &c, const DevPod &pod, const NV &v, const NumaRowR &nr,
-                                                  const DevNumaClass *classes) {
-    return filter_reasons(c, pod, v, nr, classes, 0, 0u);
+  template <int S>
+  static __device__ __forceinline__ uint32_t eval(const DevCfg &c, const DevPod &pod, const NV &v,
+                                                  const NumaRowRS<S> &nr, const DevNumaClass *classes, int nmatch,
+                                                  uint32_t mm) {
+    return filter_reasons(c, pod, v, nr, classes, nmatch, mm);
   }
   static __device__ __forceinline__ void count(uint32_t m, bool live, uint32_t slots, int32_t *rec) {
     reasons_count(m, live, slots, rec);
@@ -148,15 +95,7 @@ struct DiagReasons {
 
 hipError_t launch_reasons(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t *out,
                           uint32_t *mask, hipStream_t s) {
-  if (n_pods <= 0 || d.n <= 0) return hipSuccess;
-  if ((mask && n_pods != 1) || (!mask && !out)) return hipErrorInvalidValue;
-  const dim3 grid((d.n + DIAG_THREADS - 1) / DIAG_THREADS, (n_pods + DIAG_PT - 1) / DIAG_PT);
-  if (grid.y > 65535u) return hipErrorInvalidValue;
-  if (c.resv)
-    hipLaunchKernelGGL(k_reasons<KOORDHIP_RESV_SLOTS_MAX>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, n_pods, out, mask);
-  else
-    hipLaunchKernelGGL(k_reasons<1>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, n_pods, out, mask);
-  return hipGetLastError();
+  return launch_current<DiagReasons>(c, d, pods, n_pods, out, mask, s);
 }
 
 hipError_t launch_reasons_replay(const DevCfg &c, const DevNodes &d, const DevPod *pods, const uint64_t *cpus,

@@ -153,6 +153,31 @@ def test_fetch_reasons_prefix(Engine):
     assert_records_equal(got, m.rec[:k])
 
 
+def test_kinds_interleaved_share_the_workspaces(Engine):
+    """The six calls of both kinds on one engine, twice round: they share the
+    record and list workspaces, whose sizes follow the kind (264-B then 136-B
+    records, 4-B then 1-B planes), so a small answer follows a large one."""
+    m = RM.case("A")
+    d = m.d
+    u = int(d.unplaced[len(d.unplaced) // 2])
+    up = d.pods[d.unplaced]
+    with Engine(d.prof, device=0) as e:
+        e.load_snapshot(d.table)
+        e.place_stream(d.pods)
+        rounds = [(e.fetch_reasons(len(d.pods)), e.fetch_diagnosis(len(d.pods)), e.fetch_node_reasons(u),
+                   e.fetch_node_status(u), e.diagnose_reasons(up), e.diagnose(up)) for _ in range(2)]
+    for got, diag, mask, status, final, final_diag in rounds:
+        assert_records_equal(got, m.rec)
+        assert np.array_equal(mask, m.mask[u])
+        assert np.array_equal(status, d.status[u])
+        assert_records_equal(final, m.final_rec[d.unplaced])
+        for f in ("feasible", "any", "first"):
+            assert np.array_equal(diag[f], d.rec[f]), f
+            assert np.array_equal(final_diag[f], d.final_rec[d.unplaced][f]), f
+    for a, b in zip(*rounds):
+        assert a.tobytes() == b.tobytes()
+
+
 # ------------------------------------------------- 3. no side effects
 def test_reasons_change_no_state(Engine):
     m = RM.case("C")
