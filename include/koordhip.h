@@ -46,11 +46,14 @@
  *                              read by frameworkext/eventhandlers/reservation_handler.go:92-94 and handed to every
  *                              PostFilter (elasticquota/plugin.go:310, reservation/plugin.go:496,
  *                              coscheduling/core/core.go:289-293)
- *   koordhip_diagnose_reasons / koordhip_node_reasons / koordhip_fetch_reasons / koordhip_fetch_node_reasons
+ *   koordhip_diagnose_reasons / koordhip_node_reasons / koordhip_fetch_reasons / koordhip_fetch_node_reasons /
+ *   koordhip_diagnose_reasons_ext / koordhip_node_reasons_ext
  *                           <- the Status reason and code behind each of those nodes: fitsRequest's
  *                              InsufficientResource list ((upstream) fit.go), nodenumaresource/plugin.go:266-363 and
- *                              resource_manager.go:244-326,442-453, reservation/plugin.go:373-440; what
- *                              FitError.Error() prints and nodesWherePreemptionMightHelp drops
+ *                              resource_manager.go:244-326,442-453, reservation/plugin.go:373-440,
+ *                              deviceshare/plugin.go:322 and reservation.go:280, (upstream) podtopologyspread and
+ *                              interpodaffinity filtering.go; what FitError.Error() prints and
+ *                              nodesWherePreemptionMightHelp drops
  *   koordhip_place_stream_ext / koordhip_eval_ext
  *                           <- the exact sequential cycle for profiles with plugins whose scores are normalized
  *                              over the feasible nodes (DefaultNormalizeScore, upstream helper/normalize_score.go)
@@ -780,11 +783,32 @@ int koordhip_node_status_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const k
  *                              node (one slot)
  *   17   RESV_AFFINITY         ErrReasonReservationAffinity                  UU
  *   18   RESV_INSUFFICIENT     ErrReasonReservationInsufficientResources     U
- *   19-31 reserved, zero (DeviceShare, extended scalars, PodTopologySpread,
- *        InterPodAffinity)
+ *   19-31 the sequential cycle's plugins, filled by koordhip_diagnose_reasons_ext
+ *        / koordhip_node_reasons_ext alone (zero from every other call):
+ *   19+j FIT_X0 .. FIT_X7      "Insufficient <extended scalar j>" (j = 0 ..    U
+ *                              KOORDHIP_NXRES-1; upstream fitsRequest over
+ *                              ScalarResources)
+ *   27   DEVICE_INSUFFICIENT   ErrInsufficientDevices, deviceshare/            U
+ *                              plugin.go:322; also "node(s) reservations
+ *                              insufficient devices", deviceshare/
+ *                              reservation.go:280 (one slot: the engine's
+ *                              device evaluation gives one verdict)
+ *   28   PTS_MISSING_LABEL     upstream ErrReasonNodeLabelNotMatch             UU
+ *   29   PTS_SKEW              upstream ErrReasonConstraintsNotMatch           U
+ *   30   IPA_AFFINITY          upstream ErrReasonAffinityRulesNotMatch         UU
+ *   31   IPA_ANTI              upstream ErrReasonAntiAffinityRulesNotMatch;    U
+ *                              also ErrReasonExistingAntiAffinityRulesNotMatch
+ *                              (one slot: koordhip_pod_ext.ipa_anti folds both)
  *
- * NodeResourcesFit reports every failing resource of fitsRequest; every other
- * plugin reports one reason, the reference's first exit. */
+ * NodeResourcesFit reports every failing resource of fitsRequest -- the FIT_*
+ * and FIT_X* slots are one plugin's; every other plugin reports one reason, the
+ * reference's first exit.  PodTopologySpread walks the pod's DoNotSchedule
+ * constraints in record order: the first whose key the node lacks gives
+ * PTS_MISSING_LABEL, the first whose skew exceeds maxSkew PTS_SKEW.
+ * InterPodAffinity checks the required affinity before the two anti-affinity
+ * checks (satisfyPodAffinity first): a node failing both reports IPA_AFFINITY.
+ * The upstream plugins are not vendored: these exits are unpinned like the
+ * rest of the upstream parity. */
 #define KOORDHIP_REASON_STATIC 0
 #define KOORDHIP_REASON_FIT_PODS 1
 #define KOORDHIP_REASON_FIT_CPU 2
@@ -806,6 +830,14 @@ int koordhip_node_status_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const k
 #define KOORDHIP_REASON_RESV_INSUFFICIENT 18
 #define KOORDHIP_REASON_COUNT 19
 #define KOORDHIP_REASON_SLOTS 32
+/* ... and the sequential cycle's (the _ext calls below) */
+#define KOORDHIP_REASON_FIT_X0 19 /* + j: extended scalar j */
+#define KOORDHIP_REASON_DEVICE_INSUFFICIENT 27
+#define KOORDHIP_REASON_PTS_MISSING_LABEL 28
+#define KOORDHIP_REASON_PTS_SKEW 29
+#define KOORDHIP_REASON_IPA_AFFINITY 30
+#define KOORDHIP_REASON_IPA_ANTI 31
+#define KOORDHIP_REASON_EXT_COUNT 32
 /* the reasons of each KOORDHIP_ST_* bit (a status bit is set iff one of its reasons is) */
 #define KOORDHIP_REASONS_OF_STATIC 0x00000001u
 #define KOORDHIP_REASONS_OF_FIT 0x0000007Eu
@@ -817,6 +849,13 @@ int koordhip_node_status_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const k
 #define KOORDHIP_REASON_UNRESOLVABLE_MASK 0x00029C01u
 /* ... and Error: NUMA_POD_ERROR */
 #define KOORDHIP_REASON_ERROR_MASK 0x00000100u
+/* the sequential cycle's groups (XFIT: NodeResourcesFit as well, one plugin with REASONS_OF_FIT) ... */
+#define KOORDHIP_REASONS_OF_XFIT 0x07F80000u
+#define KOORDHIP_REASONS_OF_DEVICE 0x08000000u
+#define KOORDHIP_REASONS_OF_PTS 0x30000000u
+#define KOORDHIP_REASONS_OF_IPA 0xC0000000u
+/* ... and the UnschedulableAndUnresolvable reasons with theirs: + PTS_MISSING_LABEL, IPA_AFFINITY */
+#define KOORDHIP_REASON_EXT_UNRESOLVABLE_MASK 0x50029C01u
 
 typedef struct koordhip_reasons { /* 264 B */
   int32_t feasible;               /* nodes with no reason set */
@@ -837,6 +876,28 @@ int koordhip_node_reasons(koordhip_ctx *ctx, const koordhip_pod *pod, uint32_t *
 int koordhip_fetch_reasons(koordhip_ctx *ctx, koordhip_reasons *out /* [n_pods] */, int32_t n_pods);
 /* koordhip_fetch_node_status' call with reason masks. */
 int koordhip_fetch_node_reasons(koordhip_ctx *ctx, int32_t pod_index, uint32_t *mask /* [n] */);
+
+/* ---- ... for the sequential cycle's profiles (additive to ABI 15: detect it
+ * by the symbols) ------------------------------------------------------------
+ * koordhip_diagnose_ext's call with reason records, for every profile and
+ * snapshot it answers for: the current state, its validation and error codes
+ * (KOORDHIP_EINVAL for reserve / reservation-operating-mode pods and for bad
+ * ext records, KOORDHIP_ESTATE without a snapshot), no engine state written
+ * (a later koordhip_fetch_diagnosis still works).  The record fills slots
+ * 19-31 too.  `first` follows koordhip_diagnose_ext's Filter order with
+ * NodeResourcesFit's FIT_* and FIT_X* reasons as one group (a node whose first
+ * failing plugin is NodeResourcesFit reports all of them); `unresolvable`
+ * counts the nodes whose first failing plugin reports a reason of
+ * KOORDHIP_REASON_EXT_UNRESOLVABLE_MASK.  RESV_INSUFFICIENT follows
+ * koordhip_diagnose_ext's RESV convention (the pod's extended scalars are part
+ * of fitsNode).  On a profile outside the sequential cycle with ext NULL the
+ * record is byte-identical to koordhip_diagnose_reasons'. */
+int koordhip_diagnose_reasons_ext(koordhip_ctx *ctx, const koordhip_pod *pods, const koordhip_pod_ext *ext /* may be NULL */,
+                                  int32_t n_pods, koordhip_reasons *out /* [n_pods] */);
+/* One pod on the current state: mask[i] = the reasons of every failing plugin
+ * on node i; its KOORDHIP_ST_* bits are koordhip_node_status_ext's. */
+int koordhip_node_reasons_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const koordhip_pod_ext *ext,
+                              uint32_t *mask /* [n] */);
 
 /* ---- preemption dry run (additive to ABI 15: detect it by the symbols) -----
  * The PostFilter of elasticquota/plugin.go:310-329: SelectVictimsOnNode

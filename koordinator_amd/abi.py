@@ -254,6 +254,22 @@ REASONS_OF_BIT = {
 }
 REASON_UNRESOLVABLE_MASK = 0x00029C01   # the UnschedulableAndUnresolvable reasons
 REASON_ERROR_MASK = 0x00000100          # the Error reason (NUMA_POD_ERROR)
+# ... and the sequential cycle's (koordhip_diagnose_reasons_ext): REASON_FIT_X0 + j is extended scalar j
+# (deviceshare.XRES[j]); the other five are one slot each
+REASON_FIT_X0 = 19
+(REASON_DEVICE_INSUFFICIENT, REASON_PTS_MISSING_LABEL, REASON_PTS_SKEW, REASON_IPA_AFFINITY,
+ REASON_IPA_ANTI) = range(27, 32)
+REASON_EXT_COUNT = 32
+# Slot order is not Filter order here (XFIT, PTS and IPA precede LoadAware): nine groups, walked in
+# FILTER_ORDER_EXT with FIT and XFIT as the one plugin they are
+REASONS_OF_BIT_EXT = dict(REASONS_OF_BIT)
+REASONS_OF_BIT_EXT.update({
+    ST_XFIT_FAIL: 0x07F80000,
+    ST_DEVICE_FAIL: 0x08000000,
+    ST_PTS_FAIL: 0x30000000,
+    ST_IPA_FAIL: 0xC0000000,
+})
+REASON_EXT_UNRESOLVABLE_MASK = 0x50029C01   # + PTS_MISSING_LABEL, IPA_AFFINITY
 # numpy twin of koordhip_reasons (264 bytes)
 REASONS_DTYPE = np.dtype([("feasible", "<i4"), ("unresolvable", "<i4"), ("first", "<i4", (REASON_SLOTS,)),
                           ("any", "<i4", (REASON_SLOTS,))])
@@ -279,6 +295,32 @@ def first_reasons(mask):
         out = np.where(take, g, out)
         done |= take
     return out
+
+
+def reasons_status_ext(mask):
+    """reasons_status() over all 32 slots: the 16-bit KOORDHIP_ST_* word (koordhip_node_status_ext's)."""
+    st = 0
+    for bit, group in REASONS_OF_BIT_EXT.items():
+        st = st | np.where((np.asarray(mask, np.uint32) & np.uint32(group)) != 0, np.uint32(bit), np.uint32(0))
+    return st
+
+
+def first_reasons_ext(mask):
+    """first_reasons() in FILTER_ORDER_EXT: NodeResourcesFit's FIT_* and FIT_X* reasons are one group."""
+    m = np.asarray(mask, np.uint32)
+    out = np.zeros_like(m)
+    done = np.zeros(m.shape, bool)
+    fit = REASONS_OF_BIT_EXT[ST_FIT_FAIL] | REASONS_OF_BIT_EXT[ST_XFIT_FAIL]
+    for bit in FILTER_ORDER_EXT:
+        if bit == ST_XFIT_FAIL:
+            continue
+        g = m & np.uint32(fit if bit == ST_FIT_FAIL else REASONS_OF_BIT_EXT[bit])
+        take = ~done & (g != 0)
+        out = np.where(take, g, out)
+        done |= take
+    return out
+
+
 # the preemption dry run (koordhip_preempt*): numpy twins of koordhip_assigned (160 bytes),
 # koordhip_preemptor (208), koordhip_preempt_node (32) and koordhip_preempt_result (56)
 PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
@@ -349,7 +391,8 @@ class KoordhipError(RuntimeError):
 _lib = None
 # additive to ABI 15 (no version bump): a build without them still loads
 ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext", "koordhip_diagnose_reasons",
-                    "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons")
+                    "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
+                    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext")
 
 
 def load_library(path: str = LIB_PATH):
@@ -403,6 +446,8 @@ def load_library(path: str = LIB_PATH):
         "koordhip_node_reasons": (C.c_int, [vp, vp, C.POINTER(C.c_uint32)]),
         "koordhip_fetch_reasons": (C.c_int, [vp, vp, C.c_int32]),
         "koordhip_fetch_node_reasons": (C.c_int, [vp, C.c_int32, C.POINTER(C.c_uint32)]),
+        "koordhip_diagnose_reasons_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp]),
+        "koordhip_node_reasons_ext": (C.c_int, [vp, vp, vp, C.POINTER(C.c_uint32)]),
         "koordhip_preempt_load_pods": (C.c_int, [vp, vp, C.c_int32, _i32p, C.c_int32]),
         "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
@@ -444,6 +489,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_diagnose", "koordhip_fetch_diagnosis", "koordhip_fetch_node_status",
     "koordhip_diagnose_ext", "koordhip_node_status_ext",
     "koordhip_diagnose_reasons", "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
+    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_preempt_stream",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",

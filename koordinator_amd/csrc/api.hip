@@ -3574,13 +3574,32 @@ int koordhip_fetch_node_reasons(koordhip_ctx *c, int32_t pod_index, uint32_t *ma
 
 // ---- ... for every profile koordhip_eval_ext evaluates (diag_ext.hip) -------
 
-// koordhip_diagnose_ext (out: n_pods records) and koordhip_node_status_ext
-// (status: one pod's [n] words): koordhip_eval_ext's validation and
-// koordhip_diagnose's, then the pods into the context's workspaces and one
-// pass of k_diag_ext.  Answers against the current state; touches neither it
-// nor diag_valid.
-static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
-                             koordhip_diag *out, uint16_t *status) {
+}  // extern "C"
+
+namespace {
+
+// the two kinds of k_diag_ext: the record, a node's word in the one-pod plane and the launch wrapper
+struct ExtStatusKind {
+  using Rec = koordhip_diag;
+  using Plane = uint16_t;
+  static constexpr auto launch = kh::launch_diag_ext;
+  static constexpr const char *who = "koordhip_diagnose_ext";
+};
+struct ExtReasonKind {
+  using Rec = koordhip_reasons;
+  using Plane = uint32_t;
+  static constexpr auto launch = kh::launch_reasons_ext;
+  static constexpr const char *who = "koordhip_diagnose_reasons_ext";
+};
+
+// koordhip_diagnose_ext / koordhip_diagnose_reasons_ext (out: n_pods records)
+// and koordhip_node_status_ext / koordhip_node_reasons_ext (status: one pod's
+// [n] words): koordhip_eval_ext's validation and koordhip_diagnose's, then the
+// pods into the context's workspaces and one pass of k_diag_ext.  Answers
+// against the current state; touches neither it nor diag_valid.
+template <class K>
+int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
+                             typename K::Rec *out, typename K::Plane *status) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (n_pods < 0) return fail(KOORDHIP_EINVAL, "n_pods < 0");
   if (n_pods == 0) return 0;
@@ -3594,7 +3613,7 @@ static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const ko
   bool reserve = false;
   if (int e = check_reserve_pods(c, pods, n_pods, &reserve)) return e;
   if (reserve)
-    return fail(KOORDHIP_EINVAL, "koordhip_diagnose_ext: reserve / reservation-operating-mode pods are not covered");
+    return fail(KOORDHIP_EINVAL, std::string(K::who) + ": reserve / reservation-operating-mode pods are not covered");
   std::vector<kh::DevPod> hp;
   if (int e = to_dev_pods(pods, n_pods, hp, ext, devshare_resv_on(c))) return e;
   // the hostname minima are reduced only when a pod has a hard constraint on a hostname key (PtsPod::hhost)
@@ -3606,11 +3625,11 @@ static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const ko
   HIP_TRY(hipSetDevice(c->device));
   const int32_t n = c->n;
   if (n == 0) {
-    if (out) std::memset(out, 0, (size_t)n_pods * sizeof(koordhip_diag));
+    if (out) std::memset(out, 0, (size_t)n_pods * sizeof(typename K::Rec));
     return 0;
   }
   const size_t xb = (size_t)n_pods * sizeof(kh::DevPodX);
-  const size_t rb = status ? (size_t)n * sizeof(uint16_t) : (size_t)n_pods * sizeof(koordhip_diag);
+  const size_t rb = status ? (size_t)n * sizeof(typename K::Plane) : (size_t)n_pods * sizeof(typename K::Rec);
   if (ext)
     if (int e = ensure(c, &c->d_diagx_podx, &c->diagx_podx_cap, xb)) return e;
   if (int e = ensure(c, &c->d_diagx_ws, &c->diagx_ws_cap, kh::diag_ext_ws_bytes(n_pods))) return e;
@@ -3618,22 +3637,37 @@ static int diagnose_ext_impl(koordhip_ctx *c, const koordhip_pod *pods, const ko
   if (ext) HIP_TRY(hipMemcpyAsync(c->d_diagx_podx, ext, xb, hipMemcpyHostToDevice, c->stream));
   const int32_t rs = (c->dc.resv && (c->cfg.score_plugins & KOORDHIP_PLUGIN_RESERVATION)) ? 1 : 0;
   return diag_rec_run(c, rb, status ? static_cast<void *>(status) : static_cast<void *>(out), [&] {
-    return kh::launch_diag_ext(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods),
-                               ext ? static_cast<const kh::DevPodX *>(c->d_diagx_podx) : nullptr, n_pods, rs, c->pts,
-                               c->ipa, c->d_diagx_ws, hhost, status ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
-                               status ? static_cast<uint16_t *>(c->d_diag_rec) : nullptr, c->stream);
+    return K::launch(c->dc, c->d, static_cast<const kh::DevPod *>(c->d_diag_pods),
+                     ext ? static_cast<const kh::DevPodX *>(c->d_diagx_podx) : nullptr, n_pods, rs, c->pts, c->ipa,
+                     c->d_diagx_ws, hhost, status ? nullptr : static_cast<int32_t *>(c->d_diag_rec),
+                     status ? static_cast<typename K::Plane *>(c->d_diag_rec) : nullptr, c->stream);
   });
 }
+
+}  // namespace
+
+extern "C" {
 
 int koordhip_diagnose_ext(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
                           koordhip_diag *out) {
   if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
-  return diagnose_ext_impl(c, pods, ext, n_pods, out, nullptr);
+  return diagnose_ext_impl<ExtStatusKind>(c, pods, ext, n_pods, out, nullptr);
 }
 
 int koordhip_node_status_ext(koordhip_ctx *c, const koordhip_pod *pod, const koordhip_pod_ext *ext, uint16_t *status) {
   if (!c || !pod || !status) return fail(KOORDHIP_EINVAL, "NULL argument");
-  return diagnose_ext_impl(c, pod, ext, 1, nullptr, status);
+  return diagnose_ext_impl<ExtStatusKind>(c, pod, ext, 1, nullptr, status);
+}
+
+int koordhip_diagnose_reasons_ext(koordhip_ctx *c, const koordhip_pod *pods, const koordhip_pod_ext *ext, int32_t n_pods,
+                                  koordhip_reasons *out) {
+  if (!c || ((!pods || !out) && n_pods > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diagnose_ext_impl<ExtReasonKind>(c, pods, ext, n_pods, out, nullptr);
+}
+
+int koordhip_node_reasons_ext(koordhip_ctx *c, const koordhip_pod *pod, const koordhip_pod_ext *ext, uint32_t *mask) {
+  if (!c || !pod || !mask) return fail(KOORDHIP_EINVAL, "NULL argument");
+  return diagnose_ext_impl<ExtReasonKind>(c, pod, ext, 1, nullptr, mask);
 }
 
 // ---- preemption dry run (preempt.hip) --------------------------------------

@@ -564,6 +564,20 @@ __device__ __forceinline__ bool xfit_filter(const DevDev &dv, const DevPodX &x, 
   return ok;
 }
 
+// ... saying which: bit j = extended scalar j fails xfit_filter's term (one
+// InsufficientResource each; 0 iff xfit_filter passes)
+__device__ __forceinline__ uint32_t xfit_reasons(const DevDev &dv, const DevPodX &x, int32_t i, int32_t n) {
+  uint32_t m = 0u;
+  if (!x.xmask) return m;
+#pragma unroll
+  for (int j = 0; j < KOORDHIP_NXRES; j++) {
+    if (!((x.xmask >> j) & 1u)) continue;
+    const int64_t a = dv.xalloc ? dv.xalloc[(size_t)j * n + i] : 0;
+    if (x.xreq[j] > a - dv.xreq[(size_t)j * n + i]) m |= 1u << j;
+  }
+  return m;
+}
+
 __device__ __forceinline__ int32_t static_raw(const DevDev &dv, int which, int32_t cls, int32_t i, int32_t n) {
   const uint16_t *s = dv.sscore[which];
   return s ? (int32_t)s[(size_t)cls * n + i] : 0;

@@ -34,4 +34,11 @@ hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pod
                            int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
                            uint16_t *status, hipStream_t s);
 
+// The same pre-passes and kernel with the reason kind: out[p] += pod p's
+// koordhip_reasons record (kReasonWords words, slots 19-31 filled), or, with
+// `mask` and n_pods == 1, that pod's [n] KOORDHIP_REASON_* masks.
+hipError_t launch_reasons_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
+                              int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
+                              uint32_t *mask, hipStream_t s);
+
 }  // namespace kh

@@ -28,6 +28,14 @@
 //                     LDS, barriers inside the pod loop and another restore.
 //                     With a status pointer (one pod) the node's 16-bit status
 //                     is stored instead.
+//   k_diag_ext<SM, ExtReasons>
+//                     the same kernel counting FitError reasons
+//                     (koordhip_reasons, all 32 slots): filter_reasons on the
+//                     same restored row | the failing extended scalars
+//                     (xfit_reasons / seq_xfit_reasons) | seq_eval's DEVICE bit
+//                     | pts_reason | ipa_reason, counted by reasons_count with
+//                     `first` in the Filter order above (first_reasons_ext);
+//                     with a plane pointer the node's 32-bit reason mask.
 //
 // None of this is cached across calls: every Reserve advances pts_cnt / ipa_cnt.
 #include <hip/hip_runtime.h>
@@ -37,6 +45,7 @@
 #include "diag.h"
 #include "diag_ext.h"
 #include "diag_kind.hpp"
+#include "reasons.h"
 #include "seq.h"
 #include "seq_eval.hpp"
 
@@ -110,17 +119,42 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_hmin(PtsArgs pa, int32_t 
 // ---------------------------------------------------------------------------
 // k_diag_ext
 
-template <int SM>
+// What k_diag_ext evaluates and counts per (pod, node): the KOORDHIP_ST_* status
+// into koordhip_diag records / 16-bit words, or the KOORDHIP_REASON_* mask into
+// koordhip_reasons records / 32-bit words.
+struct ExtStatus {
+  static constexpr bool REASONS = false;
+  static constexpr int WORDS = kDiagWords;
+  using Plane = uint16_t;
+};
+struct ExtReasons {
+  static constexpr bool REASONS = true;
+  static constexpr int WORDS = kReasonWords;
+  using Plane = uint32_t;
+};
+static_assert(KOORDHIP_REASON_FIT_X0 + KOORDHIP_NXRES == KOORDHIP_REASON_DEVICE_INSUFFICIENT &&
+                  KOORDHIP_REASONS_OF_XFIT == ((1u << KOORDHIP_NXRES) - 1u) << KOORDHIP_REASON_FIT_X0,
+              "one FIT_X slot per extended scalar");
+static_assert((KOORDHIP_REASONS_OF_XFIT | KOORDHIP_REASONS_OF_DEVICE | KOORDHIP_REASONS_OF_PTS | KOORDHIP_REASONS_OF_IPA) ==
+                      ~((1u << KOORDHIP_REASON_COUNT) - 1u) &&
+                  KOORDHIP_REASON_EXT_COUNT == KOORDHIP_REASON_SLOTS,
+              "slots 19-31 belong to the sequential cycle's plugins");
+static_assert(KOORDHIP_REASON_EXT_UNRESOLVABLE_MASK ==
+                  (KOORDHIP_REASON_UNRESOLVABLE_MASK | reason_bit(KOORDHIP_REASON_PTS_MISSING_LABEL) |
+                   reason_bit(KOORDHIP_REASON_IPA_AFFINITY)),
+              "the UnschedulableAndUnresolvable reasons");
+
+template <int SM, class K>
 __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d, const DevPod *__restrict__ pods,
                                                             const DevPodX *__restrict__ podx, int32_t n_pods,
                                                             int32_t rs, PtsArgs pa, IpaArgs ia,
                                                             const PtsSums *__restrict__ psum,
                                                             const int32_t *__restrict__ hmin, int32_t *__restrict__ out,
-                                                            uint16_t *__restrict__ status) {
+                                                            typename K::Plane *__restrict__ status) {
   constexpr int S = SM >= 2 ? kSeqSlots<SM> : 1;  // the reservation slots of filter_status' side row
   __shared__ __attribute__((aligned(16))) uint64_t spw[DIAG_PT * tile_words<DevPod>()];
   __shared__ __attribute__((aligned(16))) uint64_t sxw[DIAG_PT * DIAGX_PODX_WORDS];
-  __shared__ int32_t tab[DIAG_PT * kDiagWords];
+  __shared__ int32_t tab[DIAG_PT * K::WORDS];
   __shared__ PtsLds L;   // fsum / fpres from the call's sums; fmatch / fmin per pod (ssum: Score only, never read)
   __shared__ IpaLds IL;
   const int t = threadIdx.x;
@@ -132,7 +166,7 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d,
   } else {  // the record of a pod without koordhip_pod_ext (no device request: gpu -1 = key absent)
     for (int32_t w = t; w < np * DIAGX_PODX_WORDS; w += DIAG_THREADS) sxw[w] = (w % DIAGX_PODX_WORDS) < DR ? ~0ull : 0ull;
   }
-  for (int32_t w = t; w < np * kDiagWords; w += DIAG_THREADS) tab[w] = 0;
+  for (int32_t w = t; w < np * K::WORDS; w += DIAG_THREADS) tab[w] = 0;
   const bool pts_on = pa.filt && pa.keys > 0;
   const bool ipa_on = ia.filt && ia.ents > 0;
   if (pts_on) {
@@ -149,7 +183,8 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d,
   NV v{};
   NumaRowRS<S> nr{};
   load_filter_row(c, d, il, v, nr);
-  constexpr uint32_t bits = (1u << DIAG_STATUS_BITS) - 1u;  // every counter, whatever the profile
+  // the status counters: every one, whatever the profile; the reason slots: those the profile can produce
+  const uint32_t bits = K::REASONS ? reason_slots_ext(c, pts_on, ipa_on) : (1u << DIAG_STATUS_BITS) - 1u;
   for (int32_t q = 0; q < np; q++) {  // wave-uniform: the ballots and the barriers are valid
     const DevPod &pod = sp[q];
     const DevPodX &x = sx[q];
@@ -157,6 +192,8 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d,
     int nmatch = 0;
     uint32_t mm = 0;
     ResvXS rx = no_rx();
+    uint32_t xm = 0u;  // (reasons) the failing extended scalars, as seq_eval's XFIT bit sees them
+    if constexpr (K::REASONS) xm = xfit_reasons(d.dv, x, il, d.n);
     if constexpr (S > 1) {
       if (c.resv) {
         // the cycle's restore: every plugin sees the restored node, with the extended
@@ -166,14 +203,30 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d,
         // filterWithReservations' fitsNode covers the pod's extended scalars on every node.  Where no
         // reservation holds devices they are the node's own: a node failing xfit_filter fails the fit of
         // every matched Aligned / Restricted reservation -- a ResvXS naming no slot (h = S) without RX_FIT_O.
-        if (rx.h < 0 && !xfit_filter(d.dv, x, il, d.n)) rx = ResvXS{S, RX_FIT_H | RX_LE | RX_XFIT, 0, 0};
+        if constexpr (K::REASONS) {
+          if (rx.h >= 0) xm = seq_xfit_reasons(d, pod, x, nr, il);  // on the restored scalars
+          else if (xm) rx = ResvXS{S, RX_FIT_H | RX_LE | RX_XFIT, 0, 0};
+        } else {
+          if (rx.h < 0 && !xfit_filter(d.dv, x, il, d.n)) rx = ResvXS{S, RX_FIT_H | RX_LE | RX_XFIT, 0, 0};
+        }
       }
     }
-    uint32_t st = filter_status(c, pod, w, nr, d.nu.cls, nmatch, mm, rx);
+    // the base plugins on the same restored row and ResvXS, as status bits or as reasons
+    uint32_t st;
+    if constexpr (K::REASONS)
+      st = filter_reasons(c, pod, w, nr, d.nu.cls, nmatch, mm, rx);
+    else
+      st = filter_status(c, pod, w, nr, d.nu.cls, nmatch, mm, rx);
     int32_t raw[KOORDHIP_NEXT_PLUGINS];
     uint8_t sq = 0;
     (void)seq_eval<SM>(c, d, pod, x, il, rs != 0, raw, &sq);  // XFIT, DEVICE, RESV of a reserve pod
-    st |= sq;
+    if constexpr (K::REASONS) {
+      // NodeResourcesFit reports every failing scalar; DeviceShare one slot for seq_eval's verdict
+      if (c.filt & KOORDHIP_PLUGIN_FIT) st |= xm << KOORDHIP_REASON_FIT_X0;
+      if (sq & KOORDHIP_ST_DEVICE_FAIL) st |= reason_bit(KOORDHIP_REASON_DEVICE_INSUFFICIENT);
+    } else {
+      st |= sq;
+    }
     // PodTopologySpread's Filter half only: pts_prep then never reads the Score's ssum
     PtsPod pq = pts_pod(pa, x);
     pq.soft = pq.skeys = 0u;
@@ -181,28 +234,45 @@ __global__ __launch_bounds__(DIAG_THREADS) void k_diag_ext(DevCfg c, DevNodes d,
     const bool spread = pts_on && pq.nh > 0;
     if (spread) {
       pts_prep(pa, pq, L, t);  // (ends with a barrier)
-      if (!pts_filter(pa, pq, L, pq.hhost ? hmin[p0 + q] : INT32_MAX, d.n, il)) st |= KOORDHIP_ST_PTS_FAIL;
+      const int32_t hm = pq.hhost ? hmin[p0 + q] : INT32_MAX;
+      if constexpr (K::REASONS) {
+        const int why = pts_reason(pa, pq, L, hm, d.n, il);
+        if (why) st |= reason_bit(why == 1 ? KOORDHIP_REASON_PTS_MISSING_LABEL : KOORDHIP_REASON_PTS_SKEW);
+      } else {
+        if (!pts_filter(pa, pq, L, hm, d.n, il)) st |= KOORDHIP_ST_PTS_FAIL;
+      }
     }
-    if (ipa_on && (x.ipa_aff | x.ipa_anti) != 0u && !ipa_filter(ia, IL, x, d.n, il)) st |= KOORDHIP_ST_IPA_FAIL;
+    if (ipa_on && (x.ipa_aff | x.ipa_anti) != 0u) {
+      if constexpr (K::REASONS) {
+        const int why = ipa_reason(ia, IL, x, d.n, il);
+        if (why) st |= reason_bit(why == 1 ? KOORDHIP_REASON_IPA_AFFINITY : KOORDHIP_REASON_IPA_ANTI);
+      } else {
+        if (!ipa_filter(ia, IL, x, d.n, il)) st |= KOORDHIP_ST_IPA_FAIL;
+      }
+    }
     if (status) {
-      if (live) status[i] = (uint16_t)st;
+      if (live) status[i] = (typename K::Plane)st;
+    } else if constexpr (K::REASONS) {
+      reasons_count<KOORDHIP_REASON_EXT_COUNT>(st, first_reasons_ext(st), KOORDHIP_REASON_EXT_UNRESOLVABLE_MASK, live, bits,
+                                               tab + q * K::WORDS);
     } else {
-      status_count<DIAG_STATUS_BITS>(st, first_fail(st), live, bits, tab + q * kDiagWords);
+      status_count<DIAG_STATUS_BITS>(st, first_fail(st), live, bits, tab + q * K::WORDS);
     }
     if (spread) __syncthreads();  // the next pod's pts_prep overwrites fmatch / fmin
   }
   __syncthreads();
-  if (!status) diag_flush<kDiagWords>(tab, np, out + (size_t)p0 * kDiagWords);
+  if (!status) diag_flush<K::WORDS>(tab, np, out + (size_t)p0 * K::WORDS);
 }
 
 // ---------------------------------------------------------------------------
 // host-side launch wrapper
 
-hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
-                           int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
-                           uint16_t *status, hipStream_t s) {
+template <class K>
+static hipError_t launch_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
+                             int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
+                             typename K::Plane *plane, hipStream_t s) {
   if (n_pods <= 0 || d.n <= 0) return hipSuccess;
-  if ((status && n_pods != 1) || (!status && !out) || !ws) return hipErrorInvalidValue;
+  if ((plane && n_pods != 1) || (!plane && !out) || !ws) return hipErrorInvalidValue;
   const dim3 grid((d.n + DIAG_THREADS - 1) / DIAG_THREADS, (n_pods + DIAG_PT - 1) / DIAG_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
   PtsSums *psum = static_cast<PtsSums *>(ws);
@@ -219,22 +289,34 @@ hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pod
   }
   switch (seq_mode(c)) {
     case 3:
-      hipLaunchKernelGGL(k_diag_ext<3>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
-                         out, status);
+      hipLaunchKernelGGL((k_diag_ext<3, K>), grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum,
+                         hmin, out, plane);
       break;
     case 2:
-      hipLaunchKernelGGL(k_diag_ext<2>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
-                         out, status);
+      hipLaunchKernelGGL((k_diag_ext<2, K>), grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum,
+                         hmin, out, plane);
       break;
     case 1:
-      hipLaunchKernelGGL(k_diag_ext<1>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
-                         out, status);
+      hipLaunchKernelGGL((k_diag_ext<1, K>), grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum,
+                         hmin, out, plane);
       break;
     default:
-      hipLaunchKernelGGL(k_diag_ext<0>, grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum, hmin,
-                         out, status);
+      hipLaunchKernelGGL((k_diag_ext<0, K>), grid, dim3(DIAG_THREADS), 0, s, c, d, pods, podx, n_pods, rs, pts, ipa, psum,
+                         hmin, out, plane);
   }
   return hipGetLastError();
+}
+
+hipError_t launch_diag_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
+                           int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
+                           uint16_t *status, hipStream_t s) {
+  return launch_ext<ExtStatus>(c, d, pods, podx, n_pods, rs, pts, ipa, ws, hhost, out, status, s);
+}
+
+hipError_t launch_reasons_ext(const DevCfg &c, const DevNodes &d, const DevPod *pods, const DevPodX *podx, int32_t n_pods,
+                              int32_t rs, const PtsArgs &pts, const IpaArgs &ipa, void *ws, bool hhost, int32_t *out,
+                              uint32_t *mask, hipStream_t s) {
+  return launch_ext<ExtReasons>(c, d, pods, podx, n_pods, rs, pts, ipa, ws, hhost, out, mask, s);
 }
 
 }  // namespace kh

@@ -1,6 +1,7 @@
 // diag_kind.hpp -- what the diagnosis kernels share.  For diag.hip, reasons.hip
 // and diag_ext.hip: the tile shape, the pod-tile stager, the load of the row
-// the Filter reads, the status counting and the LDS-table flush.  For diag.hip
+// the Filter reads, the status counting, the reason counting (reasons.hip and
+// diag_ext.hip's reason kind) and the LDS-table flush.  For diag.hip
 // and reasons.hip also their two kernels, parameterised on what they evaluate
 // and count per (pod, node):
 //   k_diag_current<K, S>   pods against the current state
@@ -110,6 +111,99 @@ __device__ __forceinline__ void diag_flush(const int32_t *tab, int32_t np, int32
   for (int32_t w = threadIdx.x; w < np * W; w += DIAG_THREADS) {
     const int32_t x = tab[w];
     if (x) atomicAdd(&out[w], x);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// the reason kind's counting (reasons.hip, and diag_ext.hip's reason variant)
+
+constexpr int RS_UNRES = (int)(offsetof(koordhip_reasons, unresolvable) / sizeof(int32_t));
+constexpr int RS_FIRST = (int)(offsetof(koordhip_reasons, first) / sizeof(int32_t));
+constexpr int RS_ANY = (int)(offsetof(koordhip_reasons, any) / sizeof(int32_t));
+
+// The reasons of the first failing plugin in the framework's Filter order
+// STATIC -> FIT -> LA -> NUMA -> RESV (koordhip.h): the plugins' slots lie in
+// that order, so it is the group of the lowest set bit.
+__device__ __forceinline__ uint32_t first_reasons(uint32_t m) {
+  const uint32_t low = m & (0u - m);
+  const uint32_t g = (low & KOORDHIP_REASONS_OF_STATIC) ? KOORDHIP_REASONS_OF_STATIC
+                     : (low & KOORDHIP_REASONS_OF_FIT)  ? KOORDHIP_REASONS_OF_FIT
+                     : (low & KOORDHIP_REASONS_OF_LA)   ? KOORDHIP_REASONS_OF_LA
+                     : (low & KOORDHIP_REASONS_OF_NUMA) ? KOORDHIP_REASONS_OF_NUMA
+                                                        : KOORDHIP_REASONS_OF_RESV;
+  return m & g;
+}
+
+// ... with the sequential cycle's plugins, first_fail's order: STATIC -> FIT u
+// XFIT (one plugin) -> PTS -> IPA -> LA -> NUMA -> DEVICE -> RESV.  The slots
+// 19-31 do not lie in that order, so the groups are walked.
+constexpr uint32_t first_reasons_ext(uint32_t m) {
+  constexpr uint32_t order[8] = {KOORDHIP_REASONS_OF_STATIC, KOORDHIP_REASONS_OF_FIT | KOORDHIP_REASONS_OF_XFIT,
+                                 KOORDHIP_REASONS_OF_PTS,    KOORDHIP_REASONS_OF_IPA,
+                                 KOORDHIP_REASONS_OF_LA,     KOORDHIP_REASONS_OF_NUMA,
+                                 KOORDHIP_REASONS_OF_DEVICE, KOORDHIP_REASONS_OF_RESV};
+  uint32_t f = 0u;
+  for (int k = 7; k >= 0; k--) f = (m & order[k]) ? (m & order[k]) : f;
+  return f;
+}
+
+// restricted to slots 0..18 it is first_reasons' rule (checked on one reason per group and on pairs of groups)
+constexpr bool first_reasons_ext_base_rule() {
+  constexpr uint32_t g[5] = {KOORDHIP_REASONS_OF_STATIC, KOORDHIP_REASONS_OF_FIT, KOORDHIP_REASONS_OF_LA,
+                             KOORDHIP_REASONS_OF_NUMA, KOORDHIP_REASONS_OF_RESV};
+  for (int a = 0; a < 5; a++)
+    for (int b = a; b < 5; b++)
+      if (first_reasons_ext(g[a] | g[b]) != g[a]) return false;
+  return true;
+}
+static_assert(first_reasons_ext_base_rule(), "STATIC -> FIT -> LA -> NUMA -> RESV on reason slots 0..18");
+
+// the reason slots the profile's Filter plugins can set (wave-uniform)
+__device__ __forceinline__ uint32_t reason_slots(const DevCfg &c) {
+  uint32_t numa = KOORDHIP_REASONS_OF_NUMA;
+  if (!c.amp) numa &= ~reason_bit(KOORDHIP_REASON_NUMA_AMP_CPU);
+  if (!c.zones) numa &= ~(reason_bit(KOORDHIP_REASON_NUMA_NO_ZONES) | reason_bit(KOORDHIP_REASON_NUMA_POLICY));
+  // without reservation columns no node has a matched reservation: only the affinity exit is left
+  const uint32_t resv = c.resv ? KOORDHIP_REASONS_OF_RESV : reason_bit(KOORDHIP_REASON_RESV_AFFINITY);
+  return ((c.filt & KOORDHIP_PLUGIN_NODE_STATIC) ? KOORDHIP_REASONS_OF_STATIC : 0u) |
+         ((c.filt & KOORDHIP_PLUGIN_FIT) ? KOORDHIP_REASONS_OF_FIT : 0u) |
+         ((c.filt & KOORDHIP_PLUGIN_LOADAWARE) ? KOORDHIP_REASONS_OF_LA : 0u) |
+         ((c.filt & KOORDHIP_PLUGIN_NUMA) ? numa : 0u) |
+         ((c.filt & KOORDHIP_PLUGIN_RESERVATION) ? resv : 0u);
+}
+
+// ... with the sequential cycle's plugins: the extended scalars belong to
+// NodeResourcesFit; DeviceShare's verdict comes from dev_eval / rc_eval, which
+// also answer for a Score-only DeviceShare; pts / ipa: their Filter is on and
+// the snapshot has their tables (k_diag_ext's pts_on / ipa_on)
+__device__ __forceinline__ uint32_t reason_slots_ext(const DevCfg &c, bool pts, bool ipa) {
+  return reason_slots(c) | ((c.filt & KOORDHIP_PLUGIN_FIT) ? KOORDHIP_REASONS_OF_XFIT : 0u) |
+         (((c.filt | c.score) & KOORDHIP_PLUGIN_DEVICESHARE) ? KOORDHIP_REASONS_OF_DEVICE : 0u) |
+         (pts ? KOORDHIP_REASONS_OF_PTS : 0u) | (ipa ? KOORDHIP_REASONS_OF_IPA : 0u);
+}
+
+// One wave's 64 nodes into a pod's LDS koordhip_reasons record: reason slots
+// 0..NSLOTS-1, of which the profile can produce `slots`; f = the reasons of the
+// node's first failing plugin, uu = the UnschedulableAndUnresolvable reasons.
+// The ballots of slots the profile cannot produce, and the first-ballot of a
+// reason no lane of the wave has, are skipped.  Called by every lane of the
+// wave (the ballots are wave-wide); lanes that are not `live` count nowhere.
+template <int NSLOTS>
+__device__ __forceinline__ void reasons_count(uint32_t m, uint32_t f, uint32_t uu_mask, bool live, uint32_t slots,
+                                              int32_t *rec) {
+  const bool l0 = __lane_id() == 0;
+  const uint64_t ok = __ballot(live && m == 0u);
+  const uint64_t uu = __ballot(live && (f & uu_mask) != 0u);
+  if (l0 && ok) atomicAdd(&rec[0], (int32_t)__popcll(ok));
+  if (l0 && uu) atomicAdd(&rec[RS_UNRES], (int32_t)__popcll(uu));
+#pragma unroll
+  for (int b = 0; b < NSLOTS; b++) {
+    if (!((slots >> b) & 1u)) continue;
+    const uint64_t ma = __ballot(live && ((m >> b) & 1u) != 0u);
+    if (!ma) continue;  // wave-uniform: no lane has the reason, so none has it first
+    const uint64_t mf = __ballot(live && ((f >> b) & 1u) != 0u);
+    if (l0) atomicAdd(&rec[RS_ANY + b], (int32_t)__popcll(ma));
+    if (l0 && mf) atomicAdd(&rec[RS_FIRST + b], (int32_t)__popcll(mf));
   }
 }
 

@@ -93,6 +93,34 @@ __device__ __forceinline__ bool ipa_filter(const IpaArgs &a, const IpaLds &L, co
   return true;
 }
 
+// ipa_filter saying why (the diagnosis of diag_ext.hip), in upstream Filter's
+// order: satisfyPodAffinity first (1, ErrReasonAffinityRulesNotMatch), then the
+// two anti-affinity checks (2, ErrReasonAntiAffinityRulesNotMatch /
+// ErrReasonExistingAntiAffinityRulesNotMatch); 0 passes.  Nonzero iff
+// ipa_filter fails, which tests anti first.
+__device__ __forceinline__ int ipa_reason(const IpaArgs &a, const IpaLds &L, const DevPodX &x, int32_t n, int32_t i) {
+  uint32_t m;
+  if (x.ipa_aff) {
+    bool exist = true;
+    m = x.ipa_aff;
+    while (m) {
+      const int32_t c = ipa_count(a, L, ipa_next(m), n, i);
+      if (c < 0) return 1;
+      if (c <= 0) exist = false;
+    }
+    if (!exist) {
+      if (!(x.ipa_flags & KOORDHIP_IPA_SELF)) return 1;
+      m = x.ipa_aff;
+      while (m)
+        if (L.tot[ipa_next(m)] != 0) return 1;
+    }
+  }
+  m = x.ipa_anti;
+  while (m)
+    if (ipa_count(a, L, ipa_next(m), n, i) > 0) return 2;
+  return 0;
+}
+
 // Score, scoring.go: the node's topologyScore = sum of w[e] x entry e's pair count
 __device__ __forceinline__ int32_t ipa_raw(const IpaArgs &a, const IpaLds &L, uint32_t score, const int32_t *w,
                                            int32_t n, int32_t i) {

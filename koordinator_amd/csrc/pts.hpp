@@ -220,6 +220,32 @@ __device__ __forceinline__ bool pts_filter(const PtsArgs &pa, const PtsPod &q, c
   return true;
 }
 
+// pts_filter's loop saying why (the diagnosis of diag_ext.hip): 0 passes, 1 the
+// first failing constraint's key is missing on the node
+// (ErrReasonNodeLabelNotMatch), 2 its skew exceeds maxSkew
+// (ErrReasonConstraintsNotMatch)
+__device__ __forceinline__ int pts_reason(const PtsArgs &pa, const PtsPod &q, const PtsLds &L, int32_t hmin, int32_t n,
+                                          int32_t i) {
+#pragma unroll
+  for (int j = 0; j < PP; j++) {
+    if (!((q.hard >> j) & 1u)) continue;
+    const int k = q.k[j];
+    const int32_t d = pa.dom[(size_t)k * n + i];
+    if (d < 0) return 1;
+    int64_t match, mn;
+    if ((pa.host >> k) & 1u) {
+      const int32_t m = pts_host_match(pa, q, k, n, i);
+      match = m < 0 ? 0 : m;
+      mn = hmin;
+    } else {
+      match = pts_bit(L.fpres[q.cls][k], d) ? L.fmatch[k][d] : 0;
+      mn = L.fmin[k];
+    }
+    if (match + q.self[j] - mn > q.skew[j]) return 2;
+  }
+  return 0;
+}
+
 // A feasible node: false = an IgnoredNode (lacks a soft key); else its
 // domains go into the thread's masks (PreScore's pairs) and count, folded
 // into the workgroup's by pts_soft_fold.

@@ -115,6 +115,38 @@ __device__ __forceinline__ ResvXS seq_resv_x(const DevNodes &d, const DevPod &p,
   return resv_scalars(d.dv, x, i, d.n, h, cls);
 }
 
+// The diagnosis' reasons-only sibling of resv_scalars: which extended scalars
+// fail its RX_XFIT term (NodeResourcesFit on the restored NodeInfo), bit j =
+// scalar j; 0 iff resv_scalars leaves RX_XFIT set.  Out of line for the same
+// reason (`inline` for the linkage only: a unit that never asks gets no copy).
+inline __device__ __noinline__ uint32_t resv_xfit_reasons(const DevDev &dv, const DevPodX &x, int32_t i, int32_t n, int cls) {
+  uint32_t m = 0u;
+  for (int j = 0; j < KOORDHIP_NXRES; j++) {
+    if (!((x.xmask >> j) & 1u)) continue;
+    const size_t at = (size_t)j * n + i;
+    const int64_t A = dv.rxa[at], D = dv.rxd[at];
+    const int64_t rem = A - D > 0 ? A - D : 0;
+    const int64_t alloc = dv.xalloc ? dv.xalloc[at] : 0, xr = dv.xreq[at];
+    if (x.xreq[j] > alloc - (xr - (cls != 0 ? A : 0) + (cls == 2 ? rem : 0))) m |= 1u << j;
+  }
+  return m;
+}
+
+// NodeResourcesFit's failing extended scalars for the pod on node i as
+// seq_eval's XFIT bit sees them: on the restored scalars where the node's
+// reservation holds devices (seq_resv_x names a slot), else xfit_reasons
+template <int S>
+__device__ __forceinline__ uint32_t seq_xfit_reasons(const DevNodes &d, const DevPod &p, const DevPodX &x,
+                                                     const NumaRowRS<S> &r, int32_t i) {
+  const int32_t h = d.dv.rxa ? d.dv.rslot[i] : -1;
+  if (h < 0 || h >= S) return xfit_reasons(d.dv, x, i, d.n);
+  int cls = 0;
+#pragma unroll
+  for (int q = 0; q < S; q++)
+    if (q == h) cls = resv_class(r.rs[q], p);
+  return resv_xfit_reasons(d.dv, x, i, d.n, cls);
+}
+
 // One node for one pod: the total of the per-node plugins (-1: some Filter
 // fails; with the Reservation plugin the ranking total of resv.hpp) and the
 // raw normalized scores.  Every column is read (the parity evaluator's rows,

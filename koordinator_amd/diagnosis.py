@@ -73,6 +73,29 @@ REASON_TEXT = {
     abi.REASON_RESV_INSUFFICIENT: "node(s) reservations insufficient resources",
 }
 assert sorted(REASON_TEXT) == list(range(abi.REASON_COUNT))
+# ... and slots 27-31 of koordhip_diagnose_reasons_ext's records (slots 19-26 are "Insufficient " + the extended
+# scalar's name, deviceshare.XRES): deviceshare/plugin.go:52, and upstream's (k8s v1.24, not vendored: unpinned)
+# podtopologyspread / interpodaffinity strings.  Two slots collapse two reference strings:
+# DEVICE_INSUFFICIENT also stands for "node(s) reservations insufficient devices" (deviceshare/reservation.go:280),
+# IPA_ANTI for "node(s) didn't satisfy existing pods anti-affinity rules".
+REASON_TEXT_EXT = {
+    abi.REASON_DEVICE_INSUFFICIENT: REASON_OF_BIT[abi.ST_DEVICE_FAIL],
+    abi.REASON_PTS_MISSING_LABEL: "node(s) didn't match pod topology spread constraints (missing required label)",
+    abi.REASON_PTS_SKEW: REASON_OF_BIT[abi.ST_PTS_FAIL],
+    abi.REASON_IPA_AFFINITY: "node(s) didn't match pod affinity rules",
+    abi.REASON_IPA_ANTI: "node(s) didn't match pod anti-affinity rules",
+}
+assert sorted(REASON_TEXT_EXT) == list(range(abi.REASON_FIT_X0 + abi.NXRES, abi.REASON_EXT_COUNT))
+
+
+def reason_text(r: int) -> str:
+    """The Status reason string of slot r (0 .. abi.REASON_EXT_COUNT - 1)."""
+    if r < abi.REASON_COUNT:
+        return REASON_TEXT[r]
+    if r < abi.REASON_FIT_X0 + abi.NXRES:
+        from .deviceshare import XRES
+        return "Insufficient " + XRES[r - abi.REASON_FIT_X0]
+    return REASON_TEXT_EXT[r]
 
 
 def fit_error_message(rec, n: int) -> str:
@@ -80,8 +103,10 @@ def fit_error_message(rec, n: int) -> str:
     unpinned) over a koordhip_reasons record: '0/N nodes are available: ' + the
     '<count> <reason>' strings of `first`, sorted as strings, joined with ', ',
     then '.'.  A node that fails NodeResourcesFit on several resources counts
-    under each, as upstream's per-reason histogram does."""
-    parts = sorted(f"{int(rec['first'][r])} {REASON_TEXT[r]}" for r in range(abi.REASON_COUNT)
+    under each, as upstream's per-reason histogram does.  Slots 19-31 (records
+    of koordhip_diagnose_reasons_ext) print alike; a record with zeros there
+    reads as before."""
+    parts = sorted(f"{int(rec['first'][r])} {reason_text(r)}" for r in range(abi.REASON_EXT_COUNT)
                    if int(rec["first"][r]) > 0)
     return f"0/{int(n)} nodes are available: " + ", ".join(parts) + "."
 

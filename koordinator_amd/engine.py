@@ -329,6 +329,34 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_fetch_node_reasons(self._ctx, int(pod_index), abi.ptr(out, C.c_uint32)))
         return out
 
+    def diagnose_reasons_ext(self, pods: np.ndarray, ext: Optional[np.ndarray] = None) -> np.ndarray:
+        """diagnose_reasons() for every profile and snapshot diagnose_ext()
+        answers for: abi.REASONS_DTYPE records with slots 19-31 filled
+        (DeviceShare, the extended scalars, PodTopologySpread,
+        InterPodAffinity), `first` and `unresolvable` as abi.first_reasons_ext
+        and abi.REASON_EXT_UNRESOLVABLE_MASK give them."""
+        pods = np.ascontiguousarray(pods, dtype=abi.POD_DTYPE)
+        x = None if ext is None else np.ascontiguousarray(ext, dtype=abi.POD_EXT_DTYPE)
+        out = np.zeros(len(pods), abi.REASONS_DTYPE)
+        abi.check(self.lib, self.lib.koordhip_diagnose_reasons_ext(self._ctx, pods.ctypes.data,
+                                                                   x.ctypes.data if x is not None else None, len(pods),
+                                                                   out.ctypes.data))
+        return out
+
+    def node_reasons_ext(self, pod, ext=None) -> np.ndarray:
+        """[n] 32-bit abi.REASON_* masks of one pod against the current state,
+        the sequential cycle's plugins included; abi.reasons_status_ext of it
+        is node_status_ext's row."""
+        pod = np.ascontiguousarray(np.atleast_1d(pod), dtype=abi.POD_DTYPE)
+        x = None if ext is None else np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        if len(pod) != 1 or (x is not None and len(x) != 1):
+            raise ValueError("node_reasons_ext takes one pod")
+        out = np.zeros(self.n, np.uint32)
+        abi.check(self.lib, self.lib.koordhip_node_reasons_ext(self._ctx, pod.ctypes.data,
+                                                               x.ctypes.data if x is not None else None,
+                                                               abi.ptr(out, C.c_uint32)))
+        return out
+
     # ---- preemption dry run (koordinator_amd.preemption builds the records)
     def preempt_load_pods(self, assigned: np.ndarray, pdb_allowed=()):
         """Upload the table of the pods that sit on the nodes (abi.ASSIGNED_DTYPE)

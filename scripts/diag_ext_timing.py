@@ -1,11 +1,12 @@
 """Host wall time of a FitError's Filter half under the DeviceShare profile: the
 cluster of `bench.py --workload deviceshare` (50k nodes, 30 % with GPUs) and
-1,000 pods with 20 % device pods, three routes alternating in one process:
+1,000 pods with 20 % device pods, the routes alternating in one process:
 
   (a) diagnose_ext of the 1,000 pods                       (k_diag_ext: 136 B per pod to the host)
+  (a') diagnose_reasons_ext of the same pods               (its reason kind: 264 B per pod, slots 19-31 filled)
   (b) eval_ext(status) of the same pods, the call alone and with the numpy
       histogram that turns its planes into records         (the only route before diagnose_ext)
-  (c) node_status_ext of one pod
+  (c) node_status_ext and node_reasons_ext of one pod
 
 Each figure is the median of --reps timed calls after --warmup untimed rounds;
 every call synchronises.  Prints one JSON line.  Run it twice to see the spread.
@@ -58,7 +59,8 @@ def main():
     synth.add_devices(table, synth.DevSpec())
     pods = synth.make_pods(synth.StreamSpec(args.pods, be_frac=c["be_frac"]), prof)
     ext = synth.make_device_ext(args.pods, synth.DevStreamSpec(frac=args.dev_frac))
-    t = {"diagnose_ext": [], "eval_ext_status": [], "eval_ext_status_histogram": [], "node_status_ext": []}
+    t = {"diagnose_ext": [], "diagnose_reasons_ext": [], "eval_ext_status": [], "eval_ext_status_histogram": [],
+         "node_status_ext": [], "node_reasons_ext": []}
     with PlacementEngine(prof, device=0) as eng:
         eng.load_snapshot(table)
         rec = None
@@ -66,18 +68,26 @@ def main():
             t0 = time.perf_counter()
             rec = eng.diagnose_ext(pods, ext)
             t1 = time.perf_counter()
+            rs = eng.diagnose_reasons_ext(pods, ext)
+            t1r = time.perf_counter()
             st = eng.eval_ext(pods, ext, status=True, scores=False)["status"]
             t2 = time.perf_counter()
             ref = histogram(st, abi.FILTER_ORDER_EXT, abi.DIAG_DTYPE)
             t3 = time.perf_counter()
             row = eng.node_status_ext(pods[0], ext[0])
             t4 = time.perf_counter()
+            mask = eng.node_reasons_ext(pods[0], ext[0])
+            t5 = time.perf_counter()
             if r >= args.warmup:
                 t["diagnose_ext"].append(t1 - t0)
-                t["eval_ext_status"].append(t2 - t1)
-                t["eval_ext_status_histogram"].append(t3 - t1)
+                t["diagnose_reasons_ext"].append(t1r - t1)
+                t["eval_ext_status"].append(t2 - t1r)
+                t["eval_ext_status_histogram"].append(t3 - t1r)
                 t["node_status_ext"].append(t4 - t3)
-        same = rec.tobytes() == ref.tobytes() and np.array_equal(row, st[0])
+                t["node_reasons_ext"].append(t5 - t4)
+        same = (rec.tobytes() == ref.tobytes() and np.array_equal(row, st[0]) and
+                np.array_equal(rs["feasible"], rec["feasible"]) and
+                np.array_equal(abi.reasons_status_ext(mask), row.astype(np.uint32)))
     out = {"nodes": args.nodes, "pods": args.pods, "dev_frac": args.dev_frac, "reps": args.reps,
            "routes_agree": bool(same)}
     for k, v in t.items():
