@@ -1076,7 +1076,7 @@ int koordhip_last_stats(koordhip_ctx *ctx, double *eval_ms, int64_t *eval_launch
 
 /* Per-kernel device time of the last place call (profile_kernels = 1: HIP
  * event pairs on the stream each kernel is launched on): the evaluation
- * (k_scan), the top-k selection (k_select_split / k_select) and the
+ * (k_scan), the top-k selection (k_select_split) and the
  * sequential resolve (k_resolve; one persistent launch per call unless the
  * context is in a local group).  Roofline accounting in bench.py. */
 typedef struct koordhip_kernel_stats {

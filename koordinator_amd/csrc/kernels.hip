@@ -20,7 +20,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 
 #include "eval.hpp"
 #include "karg.hpp"
@@ -400,7 +399,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void k_topk_merge(const uint64_t *__
 // coalesced 512-B (f64) / 256-B (i32) wave access and the R evaluations are
 // independent, so their loads overlap.  The result, score + 1 (0 =
 // infeasible), goes to the pod's row of the score matrix S (u16, a coalesced
-// 128-B store per r).  No selection here: k_select finds the pod's top-k from
+// 128-B store per r).  No selection here: k_select_split finds the pod's top-k from
 // S afterwards with one LDS histogram, which costs far less than a per-chunk
 // top-k list plus a merge of ~N/512 such lists.
 //
@@ -493,7 +492,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NM == 5 ? 2
     const int32_t i = c0 + r * 64 + lane;
     if (full || i < hi) col(row, i - lo) = (uint16_t)s[r];
   }
-  // the chunk's best value: k_select's lower bound for the pod's k-th score
+  // the chunk's best value: k_select_split's lower bound for the pod's k-th score
   int32_t mx = s[0];
 #pragma unroll
   for (int r = 1; r < R; r++) mx = max(mx, s[r]);
@@ -502,191 +501,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NM == 5 ? 2
 }
 
 // ---------------------------------------------------------------------------
-// k_scan_nm: the node-major evaluation (the default).
-//
-// k_scan above gives every (pod, chunk) pair its own wave, so each of a
-// round's P pods re-issues the loads of the same node columns: P x the
-// column VMEM instructions, served by L1/L2, and the kernel is bound by that
-// issue rate.  Here a wave owns one chunk of 64*R nodes, loads the columns
-// the union of its pod group's needs ONCE into VGPRs (lane l: nodes
-// c0 + 64r + l), and then loops over the group's pods with the pod record in
-// SGPRs (a uniform scalar load per pod).  The output is the same score matrix
-// S and chunk maxima Mx, so k_select / k_select_split are unchanged.
-//
-// A workgroup = 4 waves = 4 consecutive chunks x one pod group of `ppw` pods;
-// the host sizes ppw so the grid still holds ~2 waves per SIMD (fewer pods per
-// wave when the node table is small).  XCD-aware like k_scan: block b runs on
-// XCD b % 8 and XCD x only touches the x-th eighth of the chunk quads.
-//
-// Semantics: a pod's evaluation must see exactly the side row its own needs
-// would load (pod_needs: e.g. cls = -1 / amp = 1 / nflags = 0 when the pod's
-// NodeNUMAResource work is skipped), so the union row is narrowed per pod by
-// numa_view before the evaluation; NV fields outside a pod's needs are never
-// read by its evaluation.
-__device__ __forceinline__ uint32_t need_pack(const Need &n) {
-  return (uint32_t)n.pods | (uint32_t)n.r_cpu << 1 | (uint32_t)n.r_mem << 2 | (uint32_t)n.eph << 3 |
-         (uint32_t)n.bcpu << 4 | (uint32_t)n.bmem << 5 | (uint32_t)n.a_cpu << 6 | (uint32_t)n.a_mem << 7 |
-         (uint32_t)n.nz_cpu << 8 | (uint32_t)n.nz_mem << 9 | (uint32_t)n.la << 10 | (uint32_t)n.la_nonprod << 11 |
-         (uint32_t)n.la_prod << 12 | (uint32_t)n.numa << 13 | (uint32_t)n.numa_masks << 14 | (uint32_t)n.zones << 15 |
-         (uint32_t)n.amp << 16 | (uint32_t)n.resv << 17 | (uint32_t)n.sa << 18;
-}
-__device__ __forceinline__ Need need_unpack(uint32_t b) {
-  b = __builtin_amdgcn_readfirstlane(b);
-  Need n{};
-  n.pods = b & 1;
-  n.r_cpu = (b >> 1) & 1;
-  n.r_mem = (b >> 2) & 1;
-  n.eph = (b >> 3) & 1;
-  n.bcpu = (b >> 4) & 1;
-  n.bmem = (b >> 5) & 1;
-  n.a_cpu = (b >> 6) & 1;
-  n.a_mem = (b >> 7) & 1;
-  n.nz_cpu = (b >> 8) & 1;
-  n.nz_mem = (b >> 9) & 1;
-  n.la = (b >> 10) & 1;
-  n.la_nonprod = (b >> 11) & 1;
-  n.la_prod = (b >> 12) & 1;
-  n.numa = (b >> 13) & 1;
-  n.numa_masks = (b >> 14) & 1;
-  n.zones = (b >> 15) & 1;
-  n.amp = (b >> 16) & 1;
-  n.resv = (b >> 17) & 1;
-  n.sa = (b >> 18) & 1;
-  return n;
-}
-// OR over the wave (DPP within rows, then the row broadcasts), result in every lane
-__device__ __forceinline__ uint32_t wave_or_u32(uint32_t v) {
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-
-template <bool Z>
-__device__ __forceinline__ void numa_view(NumaRow &r, const Need &n) {
-  if (!n.numa) {
-    r.cls = -1;
-    r.nflags = 0;
-    r.amp = 1.0;
-    return;
-  }
-  if (!n.amp) r.amp = 1.0;
-  if (!(n.numa_masks || (Z && n.zones))) r.nflags = 0;
-}
-
-template <int R, int NM>
-__global__ __launch_bounds__(256) void k_scan_nm(DevCfg c, DevNodes d, const DevPod *__restrict__ pods, int32_t n_pods,
-                                                 int32_t lo, int32_t hi, int32_t nchunks, int32_t cqx, int32_t ppw,
-                                                 uint16_t *__restrict__ S, int64_t s_stride,
-                                                 uint16_t *__restrict__ Mx, int32_t m_stride) {
-  const int32_t b = blockIdx.x;
-  const int32_t xcd = b & 7, local = b >> 3;
-  const int32_t cq = xcd * cqx + local % cqx;
-  const int32_t pg = local / cqx;
-  if (cq * 4 >= nchunks) return;  // block-uniform
-  const DevNumaClass *cls = d.nu.cls;
-  if constexpr (NM != 0) {  // topology classes -> LDS (as k_scan)
-    extern __shared__ uint4 scan_cls[];
-    if (d.nu.ncls <= NUMA_LDS_CLASSES) {
-      const uint4 *src = reinterpret_cast<const uint4 *>(d.nu.cls);
-      for (int32_t x = threadIdx.x; x < d.nu.ncls * (int32_t)(sizeof(DevNumaClass) / 16); x += 256) scan_cls[x] = src[x];
-      __syncthreads();
-      cls = reinterpret_cast<const DevNumaClass *>(scan_cls);
-    }
-  }
-  const int lane = lane_id();
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int32_t chunk = cq * 4 + wave;
-  const int32_t p0 = pg * ppw, p1 = min(p0 + ppw, n_pods);
-  if (chunk >= nchunks || p0 >= p1) return;  // wave-uniform, no barrier follows
-  // the union of the group's needs: lane j evaluates pod p0 + j's needs (one
-  // round of vector loads instead of a chain of dependent scalar loads), the
-  // packed bits are OR-reduced across the wave
-  uint32_t nb = 0;
-  if (lane < p1 - p0) {
-    // the whole record in six 16-B loads issued together (pod_needs reads its
-    // fields under short-circuit conditions: field-wise loads would chain)
-    const uint4 *q = reinterpret_cast<const uint4 *>(pods + p0 + lane);
-    uint4 t[sizeof(DevPod) / 16];
-#pragma unroll
-    for (int k = 0; k < (int)(sizeof(DevPod) / 16); k++) t[k] = q[k];
-    DevPod pl;
-    __builtin_memcpy(&pl, t, sizeof(DevPod));
-    nb = need_pack(pod_needs(pl, c));
-  }
-  const Need need = need_unpack(wave_or_u32(nb));
-  const int32_t c0 = lo + chunk * (64 * R);
-  NV v[R];
-  side_row_t<NM> nr[R];
-  bool in[R];
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const int32_t i = c0 + r * 64 + lane;
-    in[r] = i < hi;
-    const int32_t ii = in[r] ? i : hi - 1;  // out-of-range lanes evaluate a valid row, stored nowhere
-    load_node(v[r], d, ii, need, c);
-    if constexpr (NM >= 3) {
-      load_numa<false>(nr[r], d, ii, need);
-      load_resv(nr[r], d.rv, ii);
-    } else if constexpr (NM != 0) {
-      load_numa<NM == 2>(nr[r], d, ii, need);
-    }
-  }
-  // pod records in SGPRs, the next one's scalar loads issued before this
-  // pod's evaluation so their latency hides behind it
-  DevPod nxt = pods[p0];
-  for (int32_t p = p0; p < p1; p++) {
-    const DevPod pod = nxt;
-    nxt = pods[min(p + 1, p1 - 1)];
-    uint16_t *row = S + (size_t)p * s_stride;
-    int32_t s[R];
-    if constexpr (NM != 0) {
-      const Need pn = pod_needs(pod, c);
-#pragma unroll
-      for (int r = 0; r < R; r++) {
-        side_row_t<NM> w = nr[r];
-        numa_view<NM == 2>(w, pn);
-        if constexpr (NM >= 3)
-          s[r] = eval_total_resv(pod, v[r], w, cls, c) + 1;
-        else
-          s[r] = eval_total_numa<NM == 2>(pod, v[r], w, cls, c) + 1;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < R; r++) s[r] = eval_total(pod, v[r], c) + 1;
-    }
-    int32_t mx = 0;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-      s[r] = in[r] ? s[r] : 0;
-      if (in[r]) col(row, c0 + r * 64 + lane - lo) = (uint16_t)s[r];
-      mx = max(mx, s[r]);
-    }
-    mx = wave_max_i32_dpp(mx);
-    if (lane == 0) Mx[(size_t)p * m_stride + chunk] = (uint16_t)mx;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// k_select: one workgroup per pod, the exact top-k of its score row.
+// The exact top-k of a pod's score row: what k_select_split and k_eval_topk share.
 //
 // Keys order by (score desc, node asc), i.e. the reference's selectHost with
 // the lowest-index tie rule.  A lower bound L <= S* comes first: the k-th
 // largest of the pod's chunk maxima (k_scan), since k distinct chunks each
 // hold a node scoring >= it -- with 128-node chunks L is close to S*.  Pass 1
-// builds the histogram of the row's scores >= L in LDS (one bin per total-
-// score value, <= 30002 bins; few atomics thanks to L); the k-th largest S*
-// follows by a top-down cumulative count, and gt = #(score > S*) < k.  Pass 2
-// walks the row in node order: scores > S* go to a small LDS buffer (rank
-// sorted at the end), ties at S* are numbered by a block prefix sum so the
-// lowest k - gt indexes are taken.  Fewer than k feasible nodes -> all of
-// them (S* = the lowest feasible value).  Output: k keys, best first, 0-padded.
-
-constexpr int SEL_THREADS = 1024;
-constexpr int SEL_WAVES = SEL_THREADS / 64;
+// builds the histogram of the scores >= L in LDS (one bin per total-score
+// value; few atomics thanks to L); the k-th largest S* follows by a top-down
+// cumulative count, and gt = #(score > S*) < k.  Pass 2 walks the row in node
+// order: scores > S* go to a small LDS buffer (rank sorted at the end), ties
+// at S* are numbered by a block prefix sum so the lowest k - gt indexes are
+// taken.  Fewer than k feasible nodes -> all of them (S* = the lowest
+// feasible value).  Output: k keys, best first, 0-padded.
 
 // inclusive block prefix sum of one value per thread (WAVES x 64 threads)
 template <int WAVES>
@@ -711,24 +538,12 @@ __device__ __forceinline__ int32_t block_scan_incl(int32_t v, int32_t *wsum, int
   *total = tot;
   return base + x;
 }
-__device__ __forceinline__ int32_t sel_scan(int32_t v, int32_t *wsum, int32_t *total) {
-  return block_scan_incl<SEL_WAVES>(v, wsum, total);
-}
 
-// Row layout: tiles of SEL_THREADS x SEL_PER nodes; thread t owns the
-// contiguous nodes [tile + t * SEL_PER, +SEL_PER), read as SEL_ITER 16-B
-// loads issued back to back (the row comes from HBM: latency, not bandwidth,
-// bounds this kernel), so numbering per thread in thread order is node order.  The per-value tests only build bit masks (unrolled, register
-// resident); the few values that pass them are handled in a rolled loop that
-// re-reads them (L2 hits).  A one-tile row (<= 65536 nodes per shard) is
-// loaded once and kept in registers for pass 2.
-constexpr int SEL_ITER = 8;
-constexpr int SEL_PER = SEL_ITER * 8;
-constexpr int32_t SEL_TILE = SEL_THREADS * SEL_PER;
-
-__device__ __forceinline__ int32_t sel_node(int32_t tile, int t, int h) {
-  return tile * SEL_TILE + t * SEL_PER + h;
-}
+// A thread owns a contiguous run of a row tile, read as 16-B loads issued back
+// to back (the row comes from HBM: latency, not bandwidth, bounds the select),
+// so numbering per thread in thread order is node order.  The per-value tests
+// only build bit masks (unrolled, register resident); the few values that
+// pass them are handled in a rolled loop that re-reads them (L2 hits).
 
 // IT 16-B loads of one thread's contiguous run of 8 * IT row values from i0
 // (values past the row end read as 0 = infeasible)
@@ -750,12 +565,9 @@ __device__ __forceinline__ void row_load(const uint16_t *row, int32_t m, int32_t
     }
   }
 }
-__device__ __forceinline__ void sel_load(const uint16_t *row, int32_t m, int32_t tile, int t, uint4 *q) {
-  row_load<SEL_ITER>(row, m, sel_node(tile, t, 0), q);
-}
 
 // bit h of the result: value h of q satisfies (v >= x) [ge] or (v == x) [eq]
-template <int IT = SEL_ITER>
+template <int IT>
 __device__ __forceinline__ uint64_t sel_mask_ge(const uint4 *q, uint32_t x) {
   uint64_t m = 0;
 #pragma unroll
@@ -769,7 +581,7 @@ __device__ __forceinline__ uint64_t sel_mask_ge(const uint4 *q, uint32_t x) {
   }
   return m;
 }
-template <int IT = SEL_ITER>
+template <int IT>
 __device__ __forceinline__ uint64_t sel_mask_eq(const uint4 *q, uint32_t x) {
   uint64_t m = 0;
 #pragma unroll
@@ -839,138 +651,14 @@ __device__ __forceinline__ void sel_walk(F count, int32_t nbins, int32_t floor, 
   }
 }
 
-__global__ __launch_bounds__(SEL_THREADS) void k_select(const uint16_t *__restrict__ S, int64_t s_stride, int32_t lo,
-                                                        int32_t m, int32_t k, int32_t nbins,
-                                                        const uint16_t *__restrict__ Mx, int32_t m_stride,
-                                                        int32_t nchunks, uint64_t *__restrict__ out,
-                                                        uint64_t *__restrict__ dbg) {
-  // dbg (diagnostic builds only, KOORDHIP_STAMPS): per-phase s_memtime sums of thread 0
-  uint64_t ts[6] = {0, 0, 0, 0, 0, 0};
-  if (dbg && threadIdx.x == 0) ts[0] = stamp();
-  extern __shared__ uint32_t hist[];  // nbins score bins, then (nbins + 1) / 2 packed u16 chunk-max bins
-  uint32_t *mhist = hist + nbins;
-  __shared__ uint64_t gtbuf[RES_MAXP];
-  __shared__ int32_t wsum[SEL_WAVES];
-  __shared__ int32_t sh_thr, sh_gt, sh_cnt_gt;
-  const int t = threadIdx.x, lane = lane_id();
-  const int32_t p = blockIdx.x;
-  const uint16_t *row = S + (size_t)p * s_stride;
-  const int32_t ntiles = (m + SEL_TILE - 1) / SEL_TILE;
-  // first tile in flight while the lower bound is computed
-  uint4 q[SEL_ITER];
-  sel_load(row, m, 0, t, q);
-  const int32_t mwords = nchunks >= k ? (nbins + 1) >> 1 : 0;
-  for (int32_t j = t; j < nbins + mwords; j += SEL_THREADS) hist[j] = 0;
-  if (t == 0) sh_cnt_gt = 0;
-  // ---- lower bound L: k-th largest chunk maximum (histogram of the chunk
-  //      maxima, then one wave walks it top-down)
-  uint32_t L = 1;
-  if (mwords) {
-    const uint16_t *mrow = Mx + (size_t)p * m_stride;
-    __syncthreads();
-    for (int32_t j = t; j < nchunks; j += SEL_THREADS) {
-      const uint32_t v = mrow[j];
-      if (v) atomicAdd(&mhist[v >> 1], 1u << (16 * (v & 1)));  // counts <= nchunks < 2^16
-    }
-    __syncthreads();
-    if (t < 64) {
-      int32_t thr, gt;
-      sel_walk<2>([&](int32_t v) { return (int32_t)((mhist[v >> 1] >> (16 * (v & 1))) & 0xFFFFu); }, nbins, 1, k, thr,
-                  gt, -1, mhist);
-      if (lane == 0) sh_thr = thr;
-    }
-    __syncthreads();
-    L = sh_thr > 1 ? (uint32_t)sh_thr : 1u;
-  }
-  __syncthreads();
-  if (dbg && t == 0) ts[1] = stamp();
-  // ---- pass 1: histogram of the scores >= L
-  for (int32_t tile = 0; tile < ntiles; tile++) {
-    if (tile > 0) sel_load(row, m, tile, t, q);
-    uint64_t hit = sel_mask_ge(q, L);
-    while (hit) {
-      const int h = __builtin_ctzll(hit);
-      hit &= hit - 1;
-      atomicAdd(&hist[row[sel_node(tile, t, h)]], 1u);
-    }
-  }
-  __syncthreads();
-  if (dbg && t == 0) ts[2] = stamp();
-  // ---- k-th largest value S*: wave 0 walks the bins top-down, 64 at a time
-  if (t < 64) {
-    int32_t thr, gt;
-    sel_walk<1>([&](int32_t v) { return (int32_t)hist[v]; }, nbins, (int32_t)L, k, thr, gt, -1, hist);
-    if (thr == 0) {  // fewer than k feasible (then L == 1): take every feasible node
-      thr = 1;
-      gt = 0;
-      for (int32_t v = 2 + lane; v < nbins; v += 64) gt += (int32_t)hist[v];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) gt += __shfl_xor(gt, off, 64);
-    }
-    if (lane == 0) {
-      sh_thr = thr;
-      sh_gt = gt;
-    }
-  }
-  __syncthreads();
-  if (dbg && t == 0) ts[3] = stamp();
-  const uint32_t thr = (uint32_t)sh_thr;
-  const int32_t gt = sh_gt, need = k - gt;
-  uint64_t *o = out + (size_t)p * k;
-  // ---- pass 2: scores > S* (fewer than k) and the lowest-index ties at S*
-  int32_t ties = 0;  // ties numbered so far (block-uniform)
-  for (int32_t tile = 0; tile < ntiles; tile++) {
-    if (ntiles > 1) sel_load(row, m, tile, t, q);
-    const uint64_t above = sel_mask_ge(q, thr + 1);
-    uint64_t eq = sel_mask_eq(q, thr);
-    for (uint64_t x = above; x;) {
-      const int h = __builtin_ctzll(x);
-      x &= x - 1;
-      const int32_t i = sel_node(tile, t, h);
-      const int32_t pos = atomicAdd(&sh_cnt_gt, 1);
-      gtbuf[pos] = ((uint64_t)row[i] << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(lo + i));
-    }
-    const int32_t mine = __popcll(eq);
-    int32_t total;
-    int32_t pos = ties + sel_scan(mine, wsum, &total) - mine;
-    while (eq && pos < need) {  // ties in node order: thread-major, then h
-      const int h = __builtin_ctzll(eq);
-      eq &= eq - 1;
-      o[gt + pos] = ((uint64_t)thr << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)(lo + sel_node(tile, t, h)));
-      pos++;
-    }
-    ties += total;
-    if (ties >= need && sh_cnt_gt >= gt) break;  // uniform: read after sel_scan's barriers, before any later add
-    __syncthreads();
-  }
-  __syncthreads();
-  if (dbg && t == 0) ts[4] = stamp();
-  // ---- gt keys in descending order, then pad
-  for (int32_t j = t; j < gt; j += SEL_THREADS) {
-    const uint64_t x = gtbuf[j];
-    int32_t rank = 0;
-    for (int32_t q2 = 0; q2 < gt; q2++) rank += gtbuf[q2] > x;
-    st_wt(&o[rank], x);
-  }
-  const int32_t filled = gt + min(need, ties);
-  for (int32_t j = filled + t; j < k; j += SEL_THREADS) o[j] = 0;
-  if (dbg && t == 0) {
-    ts[5] = stamp();
-    for (int q2 = 1; q2 < 6; q2++) atomicAdd((unsigned long long *)&dbg[8 + q2], (unsigned long long)(ts[q2] - ts[q2 - 1]));
-    atomicAdd((unsigned long long *)&dbg[8], 1ull);
-  }
-  (void)lane;
-}
-
 // ---------------------------------------------------------------------------
-// ---------------------------------------------------------------------------
-// k_select_split: the same exact top-k with G workgroups per pod.
+// k_select_split: that exact top-k with G workgroups per pod (one workgroup per
+// pod kept 32 of 256 CUs busy at the default round size, its walk over a 100 KB
+// row latency-bound: round 2).
 //
-// One workgroup per pod (k_select) keeps 32 of 256 CUs busy at the default
-// round size and its walk over a 100 KB row is latency-bound.  Here
-// workgroup (g, p) owns slice g of pod p's row (whole tiles of SPL_TILE
+// Workgroup (g, p) owns slice g of pod p's row (whole tiles of SPL_TILE
 // nodes, 16 per thread, two 16-B loads).  It derives the pod's lower bound L
-// from the chunk maxima exactly like k_select, then the exact top-k by key of
+// from the chunk maxima as described above, then the exact top-k by key of
 // its slice restricted to scores >= L: every node of the pod's top-k scores
 // >= S* >= L and has fewer than k better keys in its own slice, so the union
 // of the slice lists holds the whole answer.  Each slice list is written
@@ -1017,7 +705,7 @@ __global__ __launch_bounds__(SPL_THREADS) void k_select_split(
     const uint16_t *__restrict__ S, int64_t s_stride, int32_t lo, int32_t m, int32_t k, int32_t nbins,
     const uint16_t *__restrict__ Mx, int32_t m_stride, int32_t nchunks, int32_t G, int32_t tiles_per,
     uint64_t *__restrict__ part, uint32_t *__restrict__ cnt, uint64_t *__restrict__ out, PipeSync *__restrict__ sy,
-    int32_t sel_par, int32_t res_wait) {
+    int32_t sel_par) {
   extern __shared__ __attribute__((aligned(16))) char spl_lds[];
   SplHdr &h = *reinterpret_cast<SplHdr *>(spl_lds);
   uint64_t *mk = reinterpret_cast<uint64_t *>(spl_lds + SPL_HDR);                    // merge: G x k keys
@@ -1258,13 +946,7 @@ __global__ __launch_bounds__(SPL_THREADS) void k_select_split(
   if (sy) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (t == 0) {
-      pipe_count_pod(sy, sel_par);
-      // the next scan on this stream may read the node columns only once the
-      // resolve has written back round res_wait - 1: the launch ends no earlier
-      // (replaces a k_wait_resolved launch between this kernel and the scan)
-      if (res_wait > 0) (void)wait_at_least(&sy->res_round, res_wait, sy);
-    }
+    if (t == 0) pipe_count_pod(sy, sel_par);
   }
 }
 
@@ -1679,6 +1361,7 @@ __global__ __launch_bounds__(ETK_THREADS) __attribute__((amdgpu_waves_per_eu(NM 
     if (t == 0) pipe_count_pod(sy, sel_par);
   }
   }  // merged pods g
+  // (res_wait is always 0: without this dead wait most instantiations spill more SGPRs, some more scratch)
   if (sy && res_wait > 0 && t == 0) (void)wait_at_least(&sy->res_round, res_wait, sy);
 }
 
@@ -1688,7 +1371,7 @@ __global__ __launch_bounds__(ETK_THREADS) __attribute__((amdgpu_waves_per_eu(NM 
 // of the next round.
 //
 // Round r's lists (k >= 2 x round size keys per pod, best first: the exact
-// top-k of the scanned nodes) were computed by k_scan / k_select WHILE round
+// top-k of the scanned nodes) were computed by k_scan / k_select_split WHILE round
 // r-1 was resolved: they are exact for every node except M' = the nodes round
 // r-1 committed to, whose columns k_scan may have read half-updated.  A
 // Reserve only raises the columns a key depends on and every enabled score is
@@ -1890,10 +1573,6 @@ __device__ __forceinline__ uint64_t ktab_key(uint32_t v, int32_t nd) {
 // Evaluation stream, before k_scan of round r: rounds < r - 1 must be written back.
 __global__ void k_wait_resolved(PipeSync *sy, int32_t rounds) {
   if (threadIdx.x == 0) (void)wait_at_least(&sy->res_round, rounds, sy);
-}
-// Evaluation stream, after round r's lists are complete (kernel boundary = visible).
-__global__ void k_signal_lists(PipeSync *sy, int32_t par, int32_t pods) {
-  if (threadIdx.x == 0) store_release(&sy->sel[par], pods);
 }
 
 template <int NM, bool DBG>
@@ -2397,8 +2076,7 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       //      The claim table of the final valid pods has one reader, the loop's
       //      claimer() on the general path of a monotone pod with X entries above
       //      its c -- config 4: 1,420 of 4,167 rounds have one.  The loop builds
-      //      it there, at the round's first such pod (claims_stale), not here
-      //      (-DKH_CHAIN_EAGER_CLAIMS: after the last pass, every round).  Until
+      //      it there, at the round's first such pod (claims_stale), not here.  Until
       //      then ckey / cval keep the last pass's table; nothing else reads
       //      them (the helper waves read dec_*), and the end-of-round clear the
       //      next prologue's inserts need stays where it is.
@@ -2628,11 +2306,7 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
           fresh = false;  // (the resolved pods' new claims are not in the table)
           clap(2);
         }
-#ifdef KH_CHAIN_EAGER_CLAIMS
-        if (!fresh) claims();  // the loop's claimer(): the valid pods' winners
-#else
         claims_stale = !fresh;  // the loop's claimer() builds the table when a pod first probes it
-#endif
         clap(3);
         if (lane == 0) __hip_atomic_store(&sh_chain, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (dbg) c_chain += stamp() - t_c0;
@@ -3103,18 +2777,10 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       if (lane < nm) {
         const NV v = slot_row(mrow[lane]);
         mrow[lane] = v;
-#ifdef KH_PUBLISH_RELEASE
-        store_row(v, nodes(), my_node);
-#else
         store_row_wt(v, nodes(), my_node);  // write-through: no L2 write-back fence at the publish
-#endif
         if constexpr (NUMA) {
           const NR nr = mnr[lane];
-#ifdef KH_PUBLISH_RELEASE
-          store_side_row<NM>(nr, nodes(), my_node);
-#else
           store_side_row_wt<NM>(nr, nodes(), my_node);
-#endif
         }
       }
       if (lane == 0) __hip_atomic_store(&sh_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // helpers stop
@@ -3160,12 +2826,8 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
         sh_mp = nm + ns;
         // the rows were stored write-through: drain them, then the relaxed
         // agent-scope flag (Guideline 16 R1; the evaluation side acquires)
-#ifdef KH_PUBLISH_RELEASE
-        store_release(&sy->res_round, r + 1);
-#else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __hip_atomic_store(&sy->res_round, r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
       }
       if (dbg) {
         const uint64_t t_end = stamp();
@@ -3438,116 +3100,33 @@ const char *last_resolve_kernel() { return g_resolve_name; }
 
 int32_t scan_chunks(int R, int32_t lo, int32_t hi) { return hi > lo ? (hi - lo + 64 * R - 1) / (64 * R) : 0; }
 
-int32_t scan_ppw(int R, int32_t lo, int32_t hi, int32_t n_pods) {
-  const int32_t nq = (scan_chunks(R, lo, hi) + 3) / 4;
-  if (nq <= 0 || n_pods <= 0) return 1;
-  // ~2048 waves (2 per SIMD) over nq chunk quads x 4 waves
-  const int32_t groups = std::max(1, std::min(n_pods, (2048 + 4 * nq - 1) / (4 * nq)));
-  return (n_pods + groups - 1) / groups;
-}
-
 hipError_t launch_scan(int R, const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t lo,
-                       int32_t hi, uint16_t *S, int64_t s_stride, uint16_t *Mx, int32_t m_stride, int32_t ppw,
-                       hipStream_t s) {
+                       int32_t hi, uint16_t *S, int64_t s_stride, uint16_t *Mx, int32_t m_stride, hipStream_t s) {
   if (n_pods <= 0 || hi <= lo) return hipSuccess;
   const int nm = side_mode(c);
-  const bool numa = nm != 0;
   const int32_t nchunks = scan_chunks(R, lo, hi);
-  const size_t lds = (numa && d.nu.ncls <= NUMA_LDS_CLASSES) ? (size_t)d.nu.ncls * sizeof(DevNumaClass) : 0;
-  if (ppw > 0 && R <= 2 && nm < 4) {  // node-major (k_scan_nm)
-    const int32_t cqx = ((nchunks + 3) / 4 + 7) / 8;
-    const int32_t nblocks = 8 * cqx * ((n_pods + ppw - 1) / ppw);
-#define KH_SCAN_NM(RR, NN)                                                                                          \
-  note_kernel(g_eval_name, "kh::k_scan_nm<%d, %d>", RR, NN);                                                        \
-  hipLaunchKernelGGL((k_scan_nm<RR, NN>), dim3(nblocks), dim3(256), lds, s, c, d, pods, n_pods, lo, hi, nchunks, cqx, \
-                     ppw, S, s_stride, Mx, m_stride)
-    switch (nm * 2 + (R - 1)) {
-      case 0: KH_SCAN_NM(1, 0); break;
-      case 1: KH_SCAN_NM(2, 0); break;
-      case 2: KH_SCAN_NM(1, 1); break;
-      case 3: KH_SCAN_NM(2, 1); break;
-      case 4: KH_SCAN_NM(1, 2); break;
-      case 5: KH_SCAN_NM(2, 2); break;
-      case 6: KH_SCAN_NM(1, 3); break;
-      case 7: KH_SCAN_NM(2, 3); break;
-      default: return hipErrorInvalidValue;
-    }
-#undef KH_SCAN_NM
-    return hipGetLastError();
-  }
+  const size_t lds = (nm != 0 && d.nu.ncls <= NUMA_LDS_CLASSES) ? (size_t)d.nu.ncls * sizeof(DevNumaClass) : 0;
   const int32_t cpx = (nchunks + 7) / 8;
   const int32_t blocks = 8 * cpx * ((n_pods + 3) / 4);
   // pod-group-fastest block order once an XCD's eighth of the shard outgrows
   // what its L2 keeps across a sweep (measured: neutral at 50k nodes, +5 % at 200k)
   const int32_t pfast = (hi - lo) > kScanPodFastNodes ? 1 : 0;
-#define KH_SCAN(RR, NN)                                                                                            \
-  do {                                                                                                        \
-    note_kernel(g_eval_name, "kh::k_scan<%d, %d>", RR, NN);                                                      \
-    hipLaunchKernelGGL((k_scan<RR, NN>), dim3(blocks), dim3(256), lds, s, c, d, pods, n_pods, lo, hi, nchunks,  \
-                       cpx, pfast, S, s_stride, Mx, m_stride);                                                  \
-  } while (0)
-  if (nm == 5) {
-    switch (R) {
-      case 4: KH_SCAN(4, 5); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else if (nm == 4) {
-    switch (R) {
-      case 4: KH_SCAN(4, 4); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else if (nm == 3) {
-    switch (R) {
-      case 1: KH_SCAN(1, 3); break;
-      case 2: KH_SCAN(2, 3); break;
-      case 4: KH_SCAN(4, 3); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else if (nm == 2) {
-    switch (R) {
-      case 1: KH_SCAN(1, 2); break;
-      case 2: KH_SCAN(2, 2); break;
-      case 4: KH_SCAN(4, 2); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else if (numa) {
-    switch (R) {
-      case 1: KH_SCAN(1, 1); break;
-      case 2: KH_SCAN(2, 1); break;
-      case 4: KH_SCAN(4, 1); break;
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (R) {
-      case 1: KH_SCAN(1, 0); break;
-      case 2: KH_SCAN(2, 0); break;
-      case 4: KH_SCAN(4, 0); break;
-      case 8: KH_SCAN(8, 0); break;
-      default: return hipErrorInvalidValue;
-    }
+#define KH_SCAN(RR, NN)                                                                                        \
+  case NN * 16 + RR:                                                                                           \
+    note_kernel(g_eval_name, "kh::k_scan<%d, %d>", RR, NN);                                                    \
+    hipLaunchKernelGGL((k_scan<RR, NN>), dim3(blocks), dim3(256), lds, s, c, d, pods, n_pods, lo, hi, nchunks, \
+                       cpx, pfast, S, s_stride, Mx, m_stride);                                                 \
+    break
+  switch (nm * 16 + R) {
+    KH_SCAN(1, 0); KH_SCAN(2, 0); KH_SCAN(4, 0); KH_SCAN(8, 0);
+    KH_SCAN(1, 1); KH_SCAN(2, 1); KH_SCAN(4, 1);
+    KH_SCAN(1, 2); KH_SCAN(2, 2); KH_SCAN(4, 2);
+    KH_SCAN(1, 3); KH_SCAN(2, 3); KH_SCAN(4, 3);
+    KH_SCAN(4, 4);
+    KH_SCAN(4, 5);
+    default: return hipErrorInvalidValue;
   }
 #undef KH_SCAN
-  return hipGetLastError();
-}
-
-hipError_t launch_select(const uint16_t *S, int64_t s_stride, int32_t lo, int32_t m, int32_t n_pods, int32_t k,
-                         int32_t nbins, const uint16_t *Mx, int32_t m_stride, int32_t nchunks, uint64_t *out,
-                         uint64_t *dbg, hipStream_t s) {
-  if (n_pods <= 0) return hipSuccess;
-  if (k < 1 || k > RES_MAXP || nbins < 2 || nbins > 32768) return hipErrorInvalidValue;
-  if (nchunks > 65535) nchunks = 0;  // no lower bound: histogram the whole row
-  size_t lds = (size_t)nbins * sizeof(uint32_t);
-  if (lds + (size_t)((nbins + 1) / 2) * sizeof(uint32_t) > 128 * 1024)
-    nchunks = 0;  // chunk-max histogram does not fit beside the score histogram
-  if (nchunks >= k) lds += (size_t)((nbins + 1) / 2) * sizeof(uint32_t);
-  static bool attr = false;
-  if (!attr) {
-    const hipError_t e = hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
-  hipLaunchKernelGGL(k_select, dim3(n_pods), dim3(SEL_THREADS), lds, s, S, s_stride, lo, m, k, nbins, Mx, m_stride,
-                     nchunks, out, dbg);
   return hipGetLastError();
 }
 
@@ -3561,7 +3140,7 @@ int32_t select_split_groups(int32_t m, int32_t G) {
 hipError_t launch_select_split(const uint16_t *S, int64_t s_stride, int32_t lo, int32_t m, int32_t n_pods, int32_t k,
                                int32_t nbins, const uint16_t *Mx, int32_t m_stride, int32_t nchunks, int32_t G,
                                uint64_t *part, uint32_t *cnt, uint64_t *out, PipeSync *sync, int32_t sel_par,
-                               int32_t res_wait, hipStream_t s) {
+                               hipStream_t s) {
   if (n_pods <= 0) return hipSuccess;
   if (k < 1 || k > RES_MAXP || nbins < 2 || nbins > 32768 || n_pods > kSelMaxPods) return hipErrorInvalidValue;
   const int32_t ntiles = std::max<int32_t>(1, (m + SPL_TILE - 1) / SPL_TILE);
@@ -3587,10 +3166,10 @@ hipError_t launch_select_split(const uint16_t *S, int64_t s_stride, int32_t lo, 
   }
   if (pk)
     hipLaunchKernelGGL(k_select_split<true>, dim3(G, n_pods), dim3(SPL_THREADS), lds, s, S, s_stride, lo, m, k, nbins,
-                       Mx, m_stride, nchunks, G, per, part, cnt, out, sync, sel_par, res_wait);
+                       Mx, m_stride, nchunks, G, per, part, cnt, out, sync, sel_par);
   else
     hipLaunchKernelGGL(k_select_split<false>, dim3(G, n_pods), dim3(SPL_THREADS), lds, s, S, s_stride, lo, m, k, nbins,
-                       Mx, m_stride, nchunks, G, per, part, cnt, out, sync, sel_par, res_wait);
+                       Mx, m_stride, nchunks, G, per, part, cnt, out, sync, sel_par);
   return hipGetLastError();
 }
 
@@ -3610,11 +3189,8 @@ int32_t eval_topk_slices(int VT, int32_t lo, int32_t hi) {
   return hi > lo ? (hi - lo + sl - 1) / sl : 0;
 }
 
-int eval_topk_vt(int nm, int32_t n_cu, int32_t n_pods, int32_t lo, int32_t hi, int32_t k) {
-  if (const char *e = std::getenv("KOORDHIP_ETK_VT")) {
-    const int v = std::atoi(e);
-    if (v == 8 || v == 16 || v == 32) return eval_topk_slices(v, lo, hi) <= ETK_MAX_SLICES ? v : 32;
-  }
+int eval_topk_vt(int nm, int32_t n_cu, int32_t n_pods, int32_t lo, int32_t hi, int32_t k, int knob) {
+  if (knob == 8 || knob == 16 || knob == 32) return eval_topk_slices(knob, lo, hi) <= ETK_MAX_SLICES ? knob : 32;
   (void)nm;
   (void)n_cu;
   (void)n_pods;
@@ -3628,8 +3204,7 @@ int eval_topk_vt(int nm, int32_t n_cu, int32_t n_pods, int32_t lo, int32_t hi, i
 
 hipError_t launch_eval_topk(const DevCfg &c, const DevNodes &d, const DevPod *pods, int32_t n_pods, int32_t lo,
                             int32_t hi, int32_t k, int VT, uint64_t *part, int32_t *pcnt, uint32_t *arrive,
-                            uint64_t *out, PipeSync *sync, int32_t sel_par, int32_t res_wait, uint64_t *dbg,
-                            hipStream_t s) {
+                            uint64_t *out, PipeSync *sync, int32_t sel_par, int G, uint64_t *dbg, hipStream_t s) {
   if (n_pods <= 0) return hipSuccess;
   if (k < 1 || k > RES_MAXP || n_pods > kSelMaxPods) return hipErrorInvalidValue;
   const int32_t nslices = eval_topk_slices(VT, lo, hi);
@@ -3641,8 +3216,6 @@ hipError_t launch_eval_topk(const DevCfg &c, const DevNodes &d, const DevPod *po
   const int nm = side_mode(c);
   // pods per workgroup (KOORDHIP_ETK_G: 1, 2 or 4; built for the plain, NUMA
   // and one-reservation plugin sets at 8 / 16 nodes per thread)
-  int G = 1;
-  if (const char *e = std::getenv("KOORDHIP_ETK_G")) G = std::atoi(e);
   if (!(G == 2 || G == 4) || VT == 32 || !(nm == 0 || nm == 1 || nm == 3)) G = 1;
   const int32_t sl = ETK_THREADS * VT;
   // merge staging: as many candidates as the slice lists can hold, up to ETK_MERGE_KEYS
@@ -3664,7 +3237,7 @@ hipError_t launch_eval_topk(const DevCfg &c, const DevNodes &d, const DevPod *po
     }                                                                                                               \
     note_kernel(g_eval_name, "kh::k_eval_topk<%d, %d, %d, %d>", NN, VV, RR, GG);                                  \
     hipLaunchKernelGGL((k_eval_topk<NN, VV, RR, GG>), dim3(blocks), dim3(ETK_THREADS), lds, s, c, d, pods, n_pods,   \
-                       lo, hi, nslices, spx, k, part, pcnt, arrive, out, sync, sel_par, res_wait, stage_cap, dbg);  \
+                       lo, hi, nslices, spx, k, part, pcnt, arrive, out, sync, sel_par, 0, stage_cap, dbg);         \
   } while (0)
 #define KH_ETK_G(NN, VV, RR)       \
   do {                             \
@@ -3741,7 +3314,7 @@ int32_t resolve_lds_bytes(int32_t n_pods_max, int32_t k, int32_t n_nodes, int nm
 hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_desc, const DevPod *pods, int32_t total, int32_t P, int32_t k,
                           int32_t r_begin, int32_t r_end, const uint64_t *lists0, int64_t list_buf, int32_t monotone,
                           int32_t lag, PipeSync *sync, int32_t *mbuf, int32_t *out_node, uint64_t *out_cpus, uint64_t *dbg,
-                          int32_t trace, hipStream_t s) {
+                          int32_t trace, bool no_preload, bool no_key_tables, hipStream_t s) {
   if (total <= 0 || r_end <= r_begin) return hipSuccess;
   if (P > RES_MAXP_ROUND || P < 1 || k > RES_MAXP || k < 1) return hipErrorInvalidValue;
   // lag 2 (one persistent launch): M' spans two rounds, lists hold >= 3P entries
@@ -3753,8 +3326,8 @@ hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_
   // a persistent launch preloads round r+1 during round r when both copies fit
   // the largest layout that fits: key tables and the next round's preload,
   // then without the preload, then without the tables
-  const bool pre = r_end - r_begin > 1 && !std::getenv("KOORDHIP_NO_PRELOAD");
-  const bool tab = !std::getenv("KOORDHIP_NO_KEY_TABLES");
+  const bool pre = r_end - r_begin > 1 && !no_preload;
+  const bool tab = !no_key_tables;
   const bool wide = c.wide_keys != 0;
   const bool chain = nm <= 2;
   ResLds o = res_lds(P, kp, d.n, nrow, pre, tab, lag, wide, chain);
@@ -3810,11 +3383,6 @@ hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_
 
 hipError_t launch_wait_resolved(PipeSync *sync, int32_t rounds, hipStream_t s) {
   hipLaunchKernelGGL(k_wait_resolved, dim3(1), dim3(64), 0, s, sync, rounds);
-  return hipGetLastError();
-}
-
-hipError_t launch_signal_lists(PipeSync *sync, int32_t par, int32_t pods, hipStream_t s) {
-  hipLaunchKernelGGL(k_signal_lists, dim3(1), dim3(64), 0, s, sync, par, pods);
   return hipGetLastError();
 }
 

@@ -16,9 +16,8 @@ static __device__ __forceinline__ uint64_t stamp() {
 // resolve kernel (one per koordhip_place_staged call):
 //   sel[b]     pods of the rounds with parity b whose final lists are ready
 //              (cumulative; rounds alternate between two evaluation streams, so
-//              a later round may finish first) (k_select_split's
-//              merging workgroups add 1 each; k_signal_lists stores the count
-//              after a separate merge)
+//              a later round may finish first) (the merging
+//              workgroups of k_select_split / k_eval_topk / k_topk_merge add 1 each)
 //   res_round  rounds resolved + written back (k_resolve, release store)
 //   err        a side gave up waiting (watchdog): the call fails, nothing hangs
 //   ext_req    device pods placed inside the pipeline (k_ext_final, seq.hip):

@@ -30,10 +30,10 @@ constexpr int32_t cls_amax(int32_t P, int32_t K) { return (kClsTarget - K) / P; 
 // The KOORDHIP_* environment knobs of the place path, read
 // at the start of every place call (api.hip read_place_knobs).
 struct PlaceKnobs {
-  bool SERIAL = false, ROUND_LAUNCH = false, FOLD_WAIT = false, ONE_EVAL_STREAM = false, CLS_OFF = false;
+  bool SERIAL = false, ROUND_LAUNCH = false, ONE_EVAL_STREAM = false, CLS_OFF = false;
   bool SHARD_LOCAL_SIM = false, SHARD_FORCE = false, LAG1 = false, LAG2 = false;
-  bool EXT_SEQ = false, EXT_ONE = false, EXT_DEDICATED = false, EXT_ALT = false;
-  bool CHAIN_OFF = false, STAMPS = false;
+  bool EXT_SEQ = false, CHAIN_OFF = false, STAMPS = false;
+  bool NO_PRELOAD = false, NO_KEY_TABLES = false;  // the resolve's launcher (kernels.hip launch_resolve)
   int32_t EXT_LEAD = 0;       // unset: 0 (the lead is never below the lag)
   int32_t CHAIN_PASSES = 1;   // unset: 1
   int32_t TRACE_POD = -1;     // unset: -1 (no pod)
@@ -47,8 +47,6 @@ struct PlaceFacts {
   bool has_comm = false, has_comm2 = false, has_group = false;
   bool side = false, resv = false;
   int side_mode = 0;      // the kernels' node-row mode (kernels.h side_mode)
-  uint32_t cu_reserve = 0;
-  bool sel_split = true;
   bool seq_profile = false, seq_ext_only = false, seq_snap = false;
   bool staged_ext = false, staged_ext_dev = false, podx_staged = false, staged_reserve = false;
   bool resv_dev_slot = false;  // a reservation holds devices (DevNodes dv.rslot)
@@ -61,7 +59,6 @@ struct PlacePlan {
   bool seq = false;         // the sequential cycle places the batch (seq.hip); nothing below applies but P 1, lag 0
   bool ext_pipe = false;    // device pods inside the pipelined greedy
   bool serial = false;      // every launch on one stream, one resolve per round
-  bool wait_kernel = true;  // k_wait_resolved launches (false: the select's merging workgroups wait)
   bool persistent = false;  // one resolve launch for the whole stream
   bool local = false;       // a node-sharded rank evaluates the full table itself
   bool exch = false;        // the rounds' lists are all-gathered and merged
@@ -90,11 +87,9 @@ inline bool ext_pipe_eligible(const PlaceFacts &f, const PlaceKnobs &k) {
 // class-incremental lists (cls.hip): the staged pods fall into few classes
 // (byte-identical records); the second stream then runs the class builds
 // (one persistent workgroup per class: every one resident, one per CU with
-// half the CUs to spare for the resolve and the builds; not beside the
-// KOORDHIP_CU_RESERVE A/B knob, whose masks were measured to stall 202
-// class workgroups)
+// half the CUs to spare for the resolve and the builds)
 inline bool cls_eligible(const PlaceFacts &f, const PlaceKnobs &k) {
-  return f.n_classes > 0 && f.nbins <= 32768 && !k.CLS_OFF && !f.cu_reserve && f.n_classes <= f.n_cu / 2 &&
+  return f.n_classes > 0 && f.nbins <= 32768 && !k.CLS_OFF && f.n_classes <= f.n_cu / 2 &&
          f.cls_run_lds(f.n, f.monotone) <= kClsLdsBudget;
 }
 
@@ -148,10 +143,6 @@ inline PlacePlan plan_place(const PlaceFacts &f, const PlaceKnobs &k) {
   // per round; the lists are then fresher than in the pipeline, which the
   // resolve treats exactly like refreshed entries.
   p.serial = k.SERIAL;
-  // KOORDHIP_FOLD_WAIT: the split select's merging workgroups hold the stream
-  // until the resolve is far enough instead of a k_wait_resolved launch
-  // (measured 2-3 % slower: their spinning delays the launch's end)
-  p.wait_kernel = !k.FOLD_WAIT;
   p.persistent = !p.serial && !f.has_group && !k.ROUND_LAUNCH;
   // A lone single-GPU context alternates the rounds between two evaluation
   // streams (each with its own score matrix and select buffers; the resolve
@@ -168,11 +159,10 @@ inline PlacePlan plan_place(const PlaceFacts &f, const PlaceKnobs &k) {
   // (KOORDHIP_SHARD_LOCAL_SIM: a lone one-GPU context takes that decision as
   // if it were a rank of a sharded job -- the path's one-GPU test)
   const bool local_sim = f.world == 1 && !f.has_comm && k.SHARD_LOCAL_SIM;
-  p.local = (f.world > 1 || local_sim) && !f.has_group && p.persistent && f.sel_split && p.wait_kernel && cls_fit &&
-            !k.SHARD_FORCE;
+  p.local = (f.world > 1 || local_sim) && !f.has_group && p.persistent && cls_fit && !k.SHARD_FORCE;
   p.exch = (f.world > 1 || f.has_comm) && !p.local;
   // (node-sharded: the rounds of the second stream exchange on comm2)
-  p.two = p.persistent && (!p.exch || f.has_comm2) && f.sel_split && p.wait_kernel && !k.ONE_EVAL_STREAM;
+  p.two = p.persistent && (!p.exch || f.has_comm2) && !k.ONE_EVAL_STREAM;
   round_shape(f, k, &p);
   // (builds are enqueued kClsLead rounds ahead and rebuilt amax / 2 rounds before they expire)
   p.cls = p.two && !p.exch && cls_fit && cls_amax(p.P, p.K) >= 4 * kClsLead + 2;

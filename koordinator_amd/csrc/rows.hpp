@@ -24,11 +24,6 @@ __device__ __forceinline__ void load_side_row(side_row_t<NM> &r, const DevNodes 
   if constexpr (NM >= 3) load_resv(r, d.rv, i);
 }
 template <int NM>
-__device__ __forceinline__ void store_side_row(const side_row_t<NM> &r, const DevNodes &d, int32_t i) {
-  store_numa_row<NM == 2>(r, d, i);
-  if constexpr (NM >= 3) store_resv(r, d.rv, i);
-}
-template <int NM>
 __device__ __forceinline__ void store_side_row_wt(const side_row_t<NM> &r, const DevNodes &d, int32_t i) {
   store_numa_row_wt<NM == 2>(r, d, i);
   if constexpr (NM >= 3) store_resv_wt(r, d.rv, i);

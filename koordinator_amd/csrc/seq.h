@@ -62,8 +62,9 @@ hipError_t launch_commit_ext(const DevCfg &c, const DevNodes &d, const DevPod *p
 // launch_ext_final (a wait for sync->ext_req = gp + 1 and pre-evaluation e, then
 // the exact placement over the pre-evaluated values with the X nodes and the
 // commit-log rounds [xlo, xhi) evaluated again; out_node, sync->ext_done,
-// DeviceShare's Reserve without the Fit / LoadAware row, out_dev).  Every wait
-// is one workgroup on device flags; submitted in an order whose waits the
+// DeviceShare's Reserve without the Fit / LoadAware row, out_dev).  The
+// pre-evaluation's wait is a one-workgroup launch on device flags, the final's
+// grid spins itself (its first workgroup polls, the others a gate); submitted in an order whose waits the
 // launches before them satisfy (api.hip), they stay deadlock-free on one stream
 // or two.  scratch: ext_scratch_bytes(n_ext, n).
 size_t ext_scratch_bytes(int32_t n_ext, int32_t n);

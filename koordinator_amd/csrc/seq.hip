@@ -32,7 +32,6 @@
 // phase, which every block writes after it finished reading parity q.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "dev.hpp"
@@ -541,7 +540,7 @@ __device__ __noinline__ bool ext_commit_wave(const DevCfg &c, const DevNodes &d,
 // flags (ExtScr::fl), each on a 128-B line of its own (pipe.hpp: many pollers
 // of one line delay its writer): pre-evaluations finished, finals finished
 // (their ring buffer read), device commits published, the gates the first
-// workgroup of a spinning pre-evaluation / final opens for the others; relaxed
+// workgroup of a final opens for the others (EXT_GPRE: k_ext_pre's dead branch); relaxed
 // agent-scope words, each stored after the data it covers was written through
 // and drained (Guideline 16 R1).  EXT_PERM: the permutation's two counters;
 // EXT_REEV: the finals' re-evaluated nodes of the call.
@@ -557,7 +556,7 @@ enum {
   EXT_FLAGS = 224
 };
 
-// A gate waiter (every workgroup of a spinning grid but the first): polls its
+// A gate waiter (every workgroup of a final's grid but the first): polls its
 // own line only, the pipeline's error word every 64th poll (pipe.hpp: a poller
 // of the error word polls the line of sel / res_round, which the resolve and
 // the class workgroups use)
@@ -591,7 +590,9 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_pre(DevCfg c, DevNodes d, c
                                                          const int32_t *__restrict__ perm, uint32_t *__restrict__ parr,
                                                          int32_t *__restrict__ fl, PipeSync *sy, int32_t rounds,
                                                          int32_t needc, int32_t fdone, int32_t spin) {
-  if (spin) {  // the waits of k_wait_ext_pre inside the grid (no launch boundary after them)
+  // (spin is always 0, the waits run in the k_wait_ext_pre launch before this one: without this dead branch the
+  // kernel takes 4 more VGPRs and spills one more SGPR)
+  if (spin) {
     __shared__ int32_t s_ok;
     if (threadIdx.x == 0) {
       bool ok;
@@ -637,8 +638,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
                                                            int32_t *__restrict__ br, int32_t *__restrict__ out_node,
                                                            uint32_t *__restrict__ out_dev, int32_t e,
                                                            int32_t *__restrict__ fl, PipeSync *sy, uint64_t *dbg,
-                                                           int32_t spin, const int32_t *__restrict__ ext_idx,
-                                                           int32_t dlo) {
+                                                           const int32_t *__restrict__ ext_idx, int32_t dlo) {
   __shared__ uint64_t lt[EXT_RAW];
   __shared__ uint32_t xm[EXT_FCHUNK / 32];  // the chunk's X nodes
   __shared__ int32_t s_red[SEQ_THREADS / 64][8];
@@ -651,32 +651,31 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
   __shared__ int32_t s_nd, s_cd;
   const int t = threadIdx.x;
   const int32_t c0 = (int32_t)blockIdx.x * EXT_FCHUNK;
-  // spin: the grid is resident before the hand-off (launched behind the
+  // The grid spins: it is resident before the hand-off (launched behind the
   // previous final) -- the pre-evaluation is awaited and its values loaded
   // first, then the hand-off, so no launch boundary sits between the
-  // resolve's request and the fold
-  if (spin) {  // the first workgroup polls the flags and opens the gates
-    if (t == 0) {
-      if (blockIdx.x == 0) {
-        // hand-off timeline (s_memrealtime, dbg[96..100]): [96] finals whose request was set before
-        // their grid started, [97] / [99] pods whose pre-evaluation was published after the request
-        // and the time waited for it, [98] request seen -> published, [100] the current request seen
-        const bool req0 = dbg && load_relaxed(&sy->ext_req) >= gp + 1;
-        const uint64_t ta = dbg ? realtime() : 0;
-        if (req0) atomicAdd((unsigned long long *)&dbg[96], 1ull);
-        s_ok[0] = wait_at_least(&fl[EXT_PREDONE], e + 1, sy);
-        if (dbg && s_ok[0] && (req0 || load_relaxed(&sy->ext_req) >= gp + 1) && realtime() - ta > 20) {
-          atomicAdd((unsigned long long *)&dbg[97], 1ull);
-          atomicAdd((unsigned long long *)&dbg[99], (unsigned long long)(realtime() - ta));
-        }
-        if (s_ok[0]) __hip_atomic_store(&fl[EXT_GFA], e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        s_ok[0] = wait_gate(&fl[EXT_GFA], e + 1, sy);
+  // resolve's request and the fold.  The first workgroup polls the flags and
+  // opens the gates.
+  if (t == 0) {
+    if (blockIdx.x == 0) {
+      // hand-off timeline (s_memrealtime, dbg[96..100]): [96] finals whose request was set before
+      // their grid started, [97] / [99] pods whose pre-evaluation was published after the request
+      // and the time waited for it, [98] request seen -> published, [100] the current request seen
+      const bool req0 = dbg && load_relaxed(&sy->ext_req) >= gp + 1;
+      const uint64_t ta = dbg ? realtime() : 0;
+      if (req0) atomicAdd((unsigned long long *)&dbg[96], 1ull);
+      s_ok[0] = wait_at_least(&fl[EXT_PREDONE], e + 1, sy);
+      if (dbg && s_ok[0] && (req0 || load_relaxed(&sy->ext_req) >= gp + 1) && realtime() - ta > 20) {
+        atomicAdd((unsigned long long *)&dbg[97], 1ull);
+        atomicAdd((unsigned long long *)&dbg[99], (unsigned long long)(realtime() - ta));
       }
+      if (s_ok[0]) __hip_atomic_store(&fl[EXT_GFA], e + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      s_ok[0] = wait_gate(&fl[EXT_GFA], e + 1, sy);
     }
-    __syncthreads();
-    if (!s_ok[0]) return;
   }
+  __syncthreads();
+  if (!s_ok[0]) return;
   uint64_t kv[EXT_FNPT];
   int32_t rv[EXT_FNPT];
 #pragma unroll
@@ -687,7 +686,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
   }
   // The device pods [dlo, e) -- committed maybe after the pre-evaluation read
   // their nodes -- have all committed before this final runs (the finals of a
-  // stream run in order; the wait covers KOORDHIP_EXT_ALT's second stream):
+  // stream run in order, and the wait below makes it hold on any stream):
   // their nodes' device rows and extended scalars are final until this pod's
   // own Reserve, so the DeviceShare Filter / raw score and the extended-scalar
   // Fit of those nodes are evaluated now, while the hand-off is pending
@@ -714,25 +713,22 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
       s_draw[t] = min(max(raw0, 0), EXT_RAW - 1);
     }
   }
-  if (spin) {
-    if (t == 0) {
-      if (blockIdx.x == 0) {
-        // the hand-off, and the previous device pod's Reserve published (the
-        // finals alternate between two streams: final e - 1 may still commit)
-        s_ok[1] = wait_at_least(&sy->ext_req, gp + 1, sy) && (e == 0 || wait_at_least(&fl[EXT_CDONE], e, sy));
-        if (dbg) __hip_atomic_store(&dbg[100], realtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (s_ok[1]) __hip_atomic_store(&fl[EXT_GFIN], gp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      } else {
-        s_ok[1] = wait_gate(&fl[EXT_GFIN], gp + 1, sy);
-      }
+  if (t == 0) {
+    if (blockIdx.x == 0) {
+      // the hand-off, and the previous device pod's Reserve published
+      s_ok[1] = wait_at_least(&sy->ext_req, gp + 1, sy) && (e == 0 || wait_at_least(&fl[EXT_CDONE], e, sy));
+      if (dbg) __hip_atomic_store(&dbg[100], realtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (s_ok[1]) __hip_atomic_store(&fl[EXT_GFIN], gp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      s_ok[1] = wait_gate(&fl[EXT_GFIN], gp + 1, sy);
     }
-    __syncthreads();
-    if (!s_ok[1]) return;
   }
+  __syncthreads();
+  if (!s_ok[1]) return;
   uint64_t tg = 0, tm = 0, te = 0;  // (dbg: this workgroup's phase times, s_memrealtime)
   if (dbg && t == 0) tg = realtime();
   // the hand-off happened and the pre-evaluation is published (the waits
-  // above or the wait launch before this one), unless the pipeline gave up
+  // above), unless the pipeline gave up
   if (__hip_atomic_load(&sy->ext_req, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != gp + 1 ||
       __hip_atomic_load(&fl[EXT_PREDONE], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < e + 1 ||
       __hip_atomic_load(&sy->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
@@ -821,7 +817,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
     const uint32_t old = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_last = old + 1u == gridDim.x;
     if (s_last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    if (dbg && spin) {  // [102..105] per workgroup: request seen -> gate seen -> X marked -> re-evaluated -> arrived
+    if (dbg) {  // [102..105] per workgroup: request seen -> gate seen -> X marked -> re-evaluated -> arrived
       const uint64_t ts = __hip_atomic_load(&dbg[100], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), ta = realtime();
       atomicAdd((unsigned long long *)&dbg[102], (unsigned long long)(tg > ts ? tg - ts : 0));
       atomicAdd((unsigned long long *)&dbg[103], (unsigned long long)(tm - tg));
@@ -873,7 +869,7 @@ __global__ __launch_bounds__(EXT_THREADS) void k_ext_final(DevCfg c, DevNodes d,
   __syncthreads();
   if (t == 0) {
     __hip_atomic_store(&sy->ext_done, gp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (dbg && spin) {  // [98] request seen -> published; [99] / [100] pods whose pre-evaluation came later
+    if (dbg) {  // [98] request seen -> published; [99] / [100] pods whose pre-evaluation came later
       const uint64_t ts = __hip_atomic_load(&dbg[100], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       atomicAdd((unsigned long long *)&dbg[98], (unsigned long long)(realtime() - ts));
     }
@@ -912,13 +908,6 @@ __global__ void k_wait_ext_pre(PipeSync *sy, int32_t *fl, int32_t rounds, int32_
   ok = ok && (needc <= 0 || wait_at_least(&fl[EXT_CDONE], needc, sy));
   ok = ok && (fdone <= 0 || wait_at_least(&fl[EXT_FDONE], fdone, sy));
   (void)ok;
-}
-// ... and until a final may start: the resolve's hand-off of device pod gp
-// (ext_req = gp + 1) and the pod's pre-evaluation (e + 1 finished)
-__global__ void k_wait_ext_final(PipeSync *sy, int32_t *fl, int32_t want, int32_t pre) {
-  if (threadIdx.x != 0) return;
-  if (wait_at_least(&sy->ext_req, want, sy) && wait_at_least(&fl[EXT_PREDONE], pre, sy))
-    (void)(pre <= 1 || wait_at_least(&fl[EXT_CDONE], pre - 1, sy));  // (the previous device pod's Reserve)
 }
 
 // The pre-evaluation's node order: nodes holding device scalars (any xalloc
@@ -1003,13 +992,9 @@ static ExtScr ext_scr(void *scratch, int32_t n_ext, int32_t n) {
 // resident before the hand-off: no launch boundary between the resolve's
 // request and the fold); the pre-evaluations wait in a one-workgroup launch
 // ahead of each (off the critical path, and a grid of a few hundred spinning
-// workgroups would hold CUs the builds need).  KOORDHIP_EXT_WAITK: the finals
-// behind wait launches too (A/B); KOORDHIP_EXT_PRESPIN: the pre-evaluations
-// spin too (A/B).  0 / 1 / 2: none / finals / both.
-static int32_t ext_spin() {
-  static const int32_t v = std::getenv("KOORDHIP_EXT_WAITK") ? 0 : std::getenv("KOORDHIP_EXT_PRESPIN") ? 2 : 1;
-  return v;
-}
+// workgroups would hold CUs the builds need).  Finals behind wait launches
+// too measured 134.7 against 114.2 ms per step on config4dsmix (DESIGN.md
+// section 4).
 
 const uint32_t *ext_reevals(const void *scratch, int32_t n_ext, int32_t n) {
   const ExtScr x = ext_scr(const_cast<void *>(scratch), n_ext, n);
@@ -1030,12 +1015,11 @@ hipError_t launch_ext_pre(const DevCfg &c, const DevNodes &d, const DevPod *pods
   if (seq_mode(c) != 0) return hipErrorInvalidValue;  // the plain build only (the route checks it)
   const ExtScr x = ext_scr(scratch, n_ext, d.n);
   const size_t nn = (size_t)std::max(d.n, 1);
-  const int32_t spin = ext_spin() > 1;  // (pre-evaluations spin only with KOORDHIP_EXT_PRESPIN)
-  if (!spin && (rounds > 0 || needc > 0 || e >= EXT_RING))
+  if (rounds > 0 || needc > 0 || e >= EXT_RING)
     hipLaunchKernelGGL(k_wait_ext_pre, dim3(1), dim3(64), 0, s, sync, x.fl, rounds, needc, e - EXT_RING + 1);
   hipLaunchKernelGGL(k_ext_pre<0>, dim3((d.n + EXT_PCHUNK - 1) / EXT_PCHUNK), dim3(EXT_THREADS), 0, s, c, d, pods, podx,
                      e, gp, x.pk + (size_t)(e % EXT_RING) * nn, x.pr + (size_t)(e % EXT_RING) * nn, x.perm, x.parr + e,
-                     x.fl, sync, rounds, needc, e - EXT_RING + 1, spin);
+                     x.fl, sync, rounds, needc, e - EXT_RING + 1, 0);
   return hipGetLastError();
 }
 
@@ -1046,11 +1030,9 @@ hipError_t launch_ext_final(const DevCfg &c, const DevNodes &d, const DevPod *po
   if (seq_mode(c) != 0) return hipErrorInvalidValue;
   const ExtScr x = ext_scr(scratch, n_ext, d.n);
   const size_t nn = (size_t)std::max(d.n, 1);
-  const int32_t spin = ext_spin() > 0;
-  if (!spin) hipLaunchKernelGGL(k_wait_ext_final, dim3(1), dim3(64), 0, s, sync, x.fl, gp + 1, e + 1);
   hipLaunchKernelGGL(k_ext_final<0>, dim3((d.n + EXT_FCHUNK - 1) / EXT_FCHUNK), dim3(EXT_THREADS), 0, s, c, d, pods,
                      podx, gp, xlo, xhi, x.tab, x.arrive + e, x.pk + (size_t)(e % EXT_RING) * nn,
-                     x.pr + (size_t)(e % EXT_RING) * nn, out_node, out_dev, e, x.fl, sync, dbg, spin, ext_idx,
+                     x.pr + (size_t)(e % EXT_RING) * nn, out_node, out_dev, e, x.fl, sync, dbg, ext_idx,
                      std::min(std::max(dlo, 0), e));
   return hipGetLastError();
 }

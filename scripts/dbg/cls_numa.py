@@ -6,7 +6,7 @@ from koordinator_amd.config import shipped_profile, to_c_config
 from koordinator_amd.engine import PlacementEngine
 import torch
 for mode in sys.argv[1:]:
-    for k in ("KOORDHIP_CU_RESERVE", "KOORDHIP_LAG2", "KOORDHIP_CLS_OFF"):
+    for k in ("KOORDHIP_LAG2", "KOORDHIP_CLS_OFF"):
         os.environ.pop(k, None)
     if mode != "default":
         os.environ[mode] = "1"

@@ -75,7 +75,7 @@ void hand_worked() {
     for (const auto &r : rows) {
       const PlacePlan p = plan_place(lone(r.batch), none);
       CHECK(!p.seq && !p.err && p.P == r.batch && p.lag == r.lag && p.K == r.K && amax(p) == r.amax && p.cls == r.cls);
-      CHECK(p.two && p.persistent && p.wait_kernel && !p.serial && !p.local && !p.exch && !p.ext_pipe);
+      CHECK(p.two && p.persistent && !p.serial && !p.local && !p.exch && !p.ext_pipe);
       CHECK(p.rounds == (1000 + r.batch - 1) / r.batch && p.lead == p.lag && p.tstride == 1);
     }
   }
@@ -98,24 +98,20 @@ void hand_worked() {
     CHECK(plan_place(lone(24), k).lag == 1);
   }
   {  // whatever takes the second evaluation stream away: lag 1, no class lists
-    PlaceKnobs k[4];
-    k[0].SERIAL = k[1].ROUND_LAUNCH = k[2].ONE_EVAL_STREAM = k[3].FOLD_WAIT = true;
+    PlaceKnobs k[3];
+    k[0].SERIAL = k[1].ROUND_LAUNCH = k[2].ONE_EVAL_STREAM = true;
     for (const PlaceKnobs &q : k) {
       const PlacePlan p = plan_place(lone(24), q);
       CHECK(!p.two && p.lag == 1 && p.K == 48 && !p.cls);
     }
     CHECK(plan_place(lone(24), k[0]).serial && !plan_place(lone(24), k[0]).persistent);
     CHECK(!plan_place(lone(24), k[1]).serial && !plan_place(lone(24), k[1]).persistent);
-    CHECK(plan_place(lone(24), k[2]).persistent && !plan_place(lone(24), k[3]).wait_kernel);
+    CHECK(plan_place(lone(24), k[2]).persistent);
     PlaceFacts g = lone(24);
     g.has_group = true;
     g.world = 2;
     PlacePlan p = plan_place(g, none);
     CHECK(!p.two && !p.persistent && p.lag == 1 && !p.cls && p.exch && !p.local);
-    PlaceFacts s = lone(24);
-    s.sel_split = false;
-    p = plan_place(s, none);
-    CHECK(!p.two && p.persistent && p.lag == 1 && !p.cls);
   }
   {  // the class lists' own conditions
     PlaceKnobs k;
@@ -130,9 +126,6 @@ void hand_worked() {
     f.n_classes = 128;
     CHECK(plan_place(f, none).cls);
     f.nbins = 32769;
-    CHECK(!plan_place(f, none).cls);
-    f = lone(24);
-    f.cu_reserve = 1;
     CHECK(!plan_place(f, none).cls);
     f = lone(24);
     f.cls_run_lds = cls_too_large;
@@ -237,10 +230,9 @@ void hand_worked() {
 
 void grid() {
   bool PlaceKnobs::*const flags[] = {
-      &PlaceKnobs::SERIAL,    &PlaceKnobs::ROUND_LAUNCH,  &PlaceKnobs::FOLD_WAIT, &PlaceKnobs::ONE_EVAL_STREAM,
-      &PlaceKnobs::CLS_OFF,   &PlaceKnobs::SHARD_LOCAL_SIM, &PlaceKnobs::SHARD_FORCE, &PlaceKnobs::LAG1,
-      &PlaceKnobs::LAG2,      &PlaceKnobs::EXT_SEQ,       &PlaceKnobs::EXT_ONE,   &PlaceKnobs::EXT_DEDICATED,
-      &PlaceKnobs::EXT_ALT,   &PlaceKnobs::CHAIN_OFF,     &PlaceKnobs::STAMPS};
+      &PlaceKnobs::SERIAL,  &PlaceKnobs::ROUND_LAUNCH,    &PlaceKnobs::ONE_EVAL_STREAM, &PlaceKnobs::CLS_OFF,
+      &PlaceKnobs::SHARD_LOCAL_SIM, &PlaceKnobs::SHARD_FORCE, &PlaceKnobs::LAG1,        &PlaceKnobs::LAG2,
+      &PlaceKnobs::EXT_SEQ, &PlaceKnobs::CHAIN_OFF,       &PlaceKnobs::STAMPS};
   const int nf = (int)(sizeof(flags) / sizeof(flags[0]));
   const int32_t batches[] = {1, 15, 16, 24, 32, 40, 64};
   long points = 0;

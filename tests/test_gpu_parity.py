@@ -276,15 +276,14 @@ def test_rccl_one_rank_exchange(Engine, numa, n_nodes, n_pods):
 
 
 # ----------------------------------------------------------- launch modes
-@pytest.mark.parametrize("mode", ["KOORDHIP_ROUND_LAUNCH", "KOORDHIP_SERIAL", "KOORDHIP_CU_RESERVE", "KOORDHIP_ONE_EVAL_STREAM", "KOORDHIP_NO_KEY_TABLES",
-                                  "KOORDHIP_FOLD_WAIT", "KOORDHIP_SELECT_ONEWG", "KOORDHIP_LAG1",
-                                  "KOORDHIP_TOPK_R=1", "KOORDHIP_SCAN_PPW=auto", "KOORDHIP_SCAN_PPW=3"])
+@pytest.mark.parametrize("mode", ["KOORDHIP_ROUND_LAUNCH", "KOORDHIP_SERIAL", "KOORDHIP_ONE_EVAL_STREAM", "KOORDHIP_NO_KEY_TABLES",
+                                  "KOORDHIP_LAG1", "KOORDHIP_TOPK_R=1"])
 @pytest.mark.parametrize("numa", [False, True])
 def test_launch_modes_bit_exact(Engine, monkeypatch, mode, numa):
     """The per-round resolve launch (local groups), the single-stream
-    profiling order and the opt-in pipeline knobs (CU-masked streams, the wait
-    folded into the select, one select workgroup per pod) place exactly like
-    the default persistent pipeline and the oracle."""
+    profiling order and the opt-in pipeline knobs (one evaluation stream, a
+    resolve without key tables, lag 1, one node per scan lane) place exactly
+    like the default persistent pipeline and the oracle."""
     name, _, val = mode.partition("=")
     monkeypatch.setenv(name, val or "1")
     prof = shipped_profile(numa=numa)
