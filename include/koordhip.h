@@ -941,7 +941,7 @@ typedef struct koordhip_preemptor {
 #define KOORDHIP_PREEMPT_NO_VICTIMS 1   /* no pod canPreempt accepts (preempt.go:150-153) */
 #define KOORDHIP_PREEMPT_UNFIT 2        /* does not fit with every potential victim removed (:161-163) */
 #define KOORDHIP_PREEMPT_ERROR 3        /* a pod removed twice: NodeInfo.RemovePod fails, the node is dropped */
-#define KOORDHIP_PREEMPT_UNRESOLVABLE 4 /* KOORDHIP_ST_STATIC_FAIL: skipped by nodesWherePreemptionMightHelp */
+#define KOORDHIP_PREEMPT_UNRESOLVABLE 4 /* KOORDHIP_ST_STATIC_FAIL (NUMA mode: see koordhip_preempt_set_mode): skipped by nodesWherePreemptionMightHelp */
 #define KOORDHIP_PREEMPT_STATUSES 5
 
 /* One node's verdict for one preemptor.  Every field but status is 0 unless
@@ -979,14 +979,53 @@ int koordhip_preempt_load_pods(koordhip_ctx *ctx, const koordhip_assigned *a, in
  * appends them, padded with -1; with max_victims below best.n_victims the
  * list is truncated.  Profiles whose Filter is NodeResourcesFit, LoadAware
  * and the static filters on the pipelined path; KOORDHIP_EINVAL for
- * NodeNUMAResource or Reservation in the Filter, Reservation snapshots,
- * sequential-cycle profiles, reserve pods and an attached communicator;
- * KOORDHIP_ESTATE without a snapshot or a loaded table. */
+ * NodeNUMAResource (unless koordhip_preempt_set_mode below accepted it) or
+ * Reservation in the Filter, Reservation snapshots, sequential-cycle profiles,
+ * reserve pods and an attached communicator; KOORDHIP_ESTATE without a
+ * snapshot or a loaded table. */
 int koordhip_preempt(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
                      int32_t *victims /* [n_pre][max_victims] */, int32_t max_victims);
 /* One preemptor's verdict on every node (the evaluator's per-node statuses). */
 int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *pre,
                                    koordhip_preempt_node *per_node /* [n] */);
+
+/* ---- the dry run under NodeNUMAResource (additive to ABI 15: detect it by the symbol)
+ * koordhip_preempt_set_mode(ctx, KOORDHIP_PREEMPT_NUMA_FROZEN) lets the three
+ * dry-run calls (koordhip_preempt, koordhip_preempt_node_verdicts,
+ * koordhip_preempt_stream) accept NodeNUMAResource in the Filter: cpuset
+ * preemptors, topology-policy nodes, amplified nodes.  The flag stands for a
+ * semantic the host accepts by setting it.  NodeNUMAResource has no
+ * PreFilterExtensions (nodenumaresource/plugin.go:262-264), so while
+ * SelectVictimsOnNode removes and re-adds pods its state does not move:
+ *   - a victim's cpuset and zone amounts are NOT freed: a node without enough
+ *     free CPUs for a cpuset preemptor stays unfit however many cpuset pods
+ *     would be evicted;
+ *   - in koordhip_preempt_stream a nominated cpuset preemptor holds NO CPUs
+ *     and no zone amounts on its node; only its requests are on the row.
+ * The reference behaves the same way (see the TODO at plugin.go:346).
+ *
+ * Per (preemptor P, node) the plugin's Filter is split in two.  F is its
+ * verdict without filterAmplifiedCPUs, on the loaded NUMA state: one constant
+ * for the whole call.  A(w) is filterAmplifiedCPUs (plugin.go:326-363) on the
+ * hypothetical row w: it reads Requested cpu, so it moves with the walk.
+ *   - UNRESOLVABLE: KOORDHIP_ST_STATIC_FAIL as before, or NodeNUMAResource is
+ *     the first failing plugin on the row the walk starts from (Fit, LoadAware
+ *     and A pass there) and F is one of KOORDHIP_REASON_UNRESOLVABLE_MASK's
+ *     reasons (NO_TOPOLOGY, NO_ZONES, SMT_ALIGN, FULL_PCPUS_ONLY);
+ *   - every later "does P fit row w" is the Fit / LoadAware / static test
+ *     together with F passing and A(w).  A node where F fails otherwise is
+ *     NO_VICTIMS without a potential victim and UNFIT with one.
+ * Everything else (the split, the reprieve order, the pick, the stream's
+ * overlay) is unchanged.
+ *
+ * flags = 0 (the default) restores the refusal.  The mode belongs to the
+ * context: it outlives load_snapshot and koordhip_preempt_load_pods, and it is
+ * inert on a profile without NodeNUMAResource in the Filter.  KOORDHIP_EINVAL
+ * for an unknown bit.  With the flag set still KOORDHIP_EINVAL: everything
+ * koordhip_preempt lists besides NodeNUMAResource, and a preemptor with
+ * KOORDHIP_POD_NUMA_ERROR (a PreFilter error aborts the cycle: no PostFilter). */
+#define KOORDHIP_PREEMPT_NUMA_FROZEN 1u
+int koordhip_preempt_set_mode(koordhip_ctx *ctx, uint32_t flags);
 
 /* ---- sequential preemption dry run (additive to ABI 15: detect it by the symbol)
  * The same dry run for a batch whose answers have to hold together: the

@@ -327,6 +327,7 @@ PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
 ASG_NONPREEMPTIBLE, ASG_IN_QUOTA = 1, 2
 PREEMPT_CANDIDATE, PREEMPT_NO_VICTIMS, PREEMPT_UNFIT, PREEMPT_ERROR, PREEMPT_UNRESOLVABLE = range(5)
 PREEMPT_STATUSES = 5
+PREEMPT_NUMA_FROZEN = 1   # koordhip_preempt_set_mode: NodeNUMAResource in the Filter, its verdict frozen for the call
 ASSIGNED_DTYPE = np.dtype([
     ("pod", POD_DTYPE), ("node", "<i4"), ("priority", "<i4"), ("start_time", "<i8"), ("quota", "<i4"),
     ("flags", "<u4"), ("pdb_mask", "<u4"), ("reserved", "<u4"), ("qreq", "<i8", (PREEMPT_QRES,)),
@@ -392,7 +393,7 @@ _lib = None
 # additive to ABI 15 (no version bump): a build without them still loads
 ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext", "koordhip_diagnose_reasons",
                     "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
-                    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext")
+                    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext", "koordhip_preempt_set_mode")
 
 
 def load_library(path: str = LIB_PATH):
@@ -452,6 +453,7 @@ def load_library(path: str = LIB_PATH):
         "koordhip_preempt": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
         "koordhip_preempt_stream": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32, vp]),
+        "koordhip_preempt_set_mode": (C.c_int, [vp, C.c_uint32]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -491,7 +493,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_diagnose_reasons", "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
     "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
-    "koordhip_preempt_stream",
+    "koordhip_preempt_stream", "koordhip_preempt_set_mode",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

@@ -273,7 +273,10 @@ struct koordhip_ctx {
   void *d_pre_in = nullptr;        // the preemptors
   void *d_pre_out = nullptr;       // counts, partials, results, victims / the per-node verdicts
   void *d_pre_st = nullptr;        // koordhip_preempt_stream's call-scoped state (kh::StreamState)
+  void *d_pre_plane = nullptr;     // the frozen NUMA verdicts of one dry-run call (kh::launch_preempt_numa)
   size_t pre_raw_cap = 0, pre_tab_cap = 0, pre_ws_cap = 0, pre_in_cap = 0, pre_out_cap = 0, pre_st_cap = 0;
+  size_t pre_plane_cap = 0;
+  uint32_t pre_mode = 0;           // koordhip_preempt_set_mode's flags: the context's, not the snapshot's
 };
 
 namespace {
@@ -1244,7 +1247,7 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
                   (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
                   c->d_diag_rec, c->d_diag_pods, c->d_diagx_podx, c->d_diagx_ws, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out,
-                  c->d_pre_st})
+                  c->d_pre_st, c->d_pre_plane})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
     if (c->ev_res[i]) (void)hipEventDestroy(c->ev_res[i]);
@@ -3674,6 +3677,30 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
   return 0;
 }
 
+int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
+  if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
+  if (flags & ~KOORDHIP_PREEMPT_NUMA_FROZEN) return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: unknown flag bit");
+  c->pre_mode = flags;
+  return 0;
+}
+
+// NodeNUMAResource is in the Filter and the host accepted the frozen verdict
+static bool preempt_numa_mode(const koordhip_ctx *c) {
+  return (c->pre_mode & KOORDHIP_PREEMPT_NUMA_FROZEN) && (c->dc.filt & KOORDHIP_PLUGIN_NUMA);
+}
+
+// The NUMA mode's pre-pass for the uploaded preemptors; *plane stays NULL outside the mode.
+static int preempt_plane(koordhip_ctx *c, int32_t n_pre, const uint64_t **plane) {
+  *plane = nullptr;
+  if (!preempt_numa_mode(c) || n_pre <= 0 || c->n <= 0) return 0;
+  if (int e = ensure(c, &c->d_pre_plane, &c->pre_plane_cap, kh::preempt_plane_words(c->n, n_pre) * sizeof(uint64_t)))
+    return e;
+  uint64_t *w = static_cast<uint64_t *>(c->d_pre_plane);
+  HIP_TRY(kh::launch_preempt_numa(c->dc, c->d, static_cast<const kh::DevPre *>(c->d_pre_in), n_pre, w, c->stream));
+  *plane = w;
+  return 0;
+}
+
 // The checks the two dry-run calls share, and the preemptors' upload.
 static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
@@ -3683,9 +3710,10 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (c->seq || c->seq_profile)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: the profile / snapshot evaluates in the sequential cycle "
                                  "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
-  if (c->dc.filt & KOORDHIP_PLUGIN_NUMA)
+  if ((c->dc.filt & KOORDHIP_PLUGIN_NUMA) && !preempt_numa_mode(c))
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with NodeNUMAResource in the Filter (it has no "
-                                 "PreFilterExtensions: its state does not move in a dry run)");
+                                 "PreFilterExtensions: its state does not move in a dry run) unless "
+                                 "koordhip_preempt_set_mode(KOORDHIP_PREEMPT_NUMA_FROZEN) accepted that");
   if (c->dc.resv || (c->dc.filt & KOORDHIP_PLUGIN_RESERVATION))
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
                                  "not kept)");
@@ -3695,6 +3723,9 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
     pods[p] = pre[p].pod;
     if (pods[p].flags & (KOORDHIP_POD_RESERVE | KOORDHIP_POD_RESV_OPERATING))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: reserve / reservation-operating-mode pods are not covered");
+    if (preempt_numa_mode(c) && (pods[p].flags & KOORDHIP_POD_NUMA_ERROR))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: a preemptor with KOORDHIP_POD_NUMA_ERROR (a PreFilter error "
+                                   "aborts the cycle: there is no PostFilter)");
     if (pre[p].quota < -1) return fail(KOORDHIP_EINVAL, "koordhip_preempt: quota is an id >= 0, or -1 (skip)");
     if (pre[p].q_mask >> KOORDHIP_PREEMPT_QRES) return fail(KOORDHIP_EINVAL, "koordhip_preempt: q_mask bit past the quota dimensions");
     for (int r = 0; r < KOORDHIP_PREEMPT_QRES; r++)
@@ -3753,9 +3784,11 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
   const kh::DevAsg *tab = static_cast<const kh::DevAsg *>(c->d_pre_tab);
   const int32_t *off = kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n);
   const kh::DevPre *dp = static_cast<const kh::DevPre *>(c->d_pre_in);
+  const uint64_t *plane = nullptr;
+  if (int e = preempt_plane(c, n_pre, &plane)) return e;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, cb, c->stream));
   if (nv) HIP_TRY(hipMemsetAsync(d_vic, 0xFF, vb, c->stream));
-  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, c->stream));
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, plane, c->stream));
   HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, d_res, d_vic, max_victims,
                                   c->stream));
   HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
@@ -3828,12 +3861,14 @@ int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int3
   // A/B knob, read at every call: every block evaluates every preemptor again (the plain per-preemptor chain)
   const char *fe = std::getenv("KOORDHIP_PREEMPT_STREAM_FULL");
   const bool full = fe && *fe && std::strcmp(fe, "0") != 0;
+  const uint64_t *plane = nullptr;  // the verdicts of all preemptors, once, before the first
+  if (int e = preempt_plane(c, n_pre, &plane)) return e;
   HIP_TRY(hipMemsetAsync(base, 0, zero_bytes, c->stream));
   HIP_TRY(hipMemsetAsync(base + o_head, 0xFF, ff_bytes, c->stream));
   HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
                                     kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
                                     static_cast<const kh::DevPre *>(c->d_pre_in), n_pre, st, max_victims, full,
-                                    c->stream));
+                                    plane, c->stream));
   HIP_TRY(hipMemcpyAsync(out, st.res, (size_t)n_pre * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, st.victims, nv * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, sizeof(*stats), hipMemcpyDeviceToHost, c->stream));
@@ -3853,11 +3888,13 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pr
   if (int e = ensure(c, &c->d_pre_out, &c->pre_out_cap, cb + pb + vb)) return e;
   char *base = static_cast<char *>(c->d_pre_out);
   koordhip_preempt_node *d_ver = reinterpret_cast<koordhip_preempt_node *>(base + cb + pb);
+  const uint64_t *plane = nullptr;
+  if (int e = preempt_plane(c, 1, &plane)) return e;
   HIP_TRY(hipMemsetAsync(base, 0, cb, c->stream));
   HIP_TRY(kh::launch_preempt(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
                              kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
                              static_cast<const kh::DevPre *>(c->d_pre_in), 1, reinterpret_cast<int32_t *>(base),
-                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, c->stream));
+                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, plane, c->stream));
   HIP_TRY(hipMemcpyAsync(per_node, d_ver, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

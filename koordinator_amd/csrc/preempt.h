@@ -54,10 +54,19 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
 // The dry run of pre[0, n_pre) on the current rows.  count [n_pre][5] (zeroed by
 // the caller) receives the nodes per status, part [n_pre][preempt_blocks(n)]
 // the workgroups' best candidates; per_node (n_pre = 1 only, may be NULL) every
-// node's verdict.
+// node's verdict.  plane: NULL, or with NodeNUMAResource in the Filter the
+// words launch_preempt_numa wrote for these preemptors (the walk then reads the
+// plugin's verdict there and evaluates filterAmplifiedCPUs on every row).
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, hipStream_t s);
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, hipStream_t s);
+// The frozen NUMA verdict plane of pre[0, n_pre): plane [n_pre][2][ceil(n / 64)]
+// u64 (preempt_plane_words), bit b of word w is node 64 w + b; [p][0]: the
+// NodeNUMAResource Filter without filterAmplifiedCPUs fails on the loaded NUMA
+// row, [p][1]: with one of KOORDHIP_REASON_UNRESOLVABLE_MASK's reasons.
+size_t preempt_plane_words(int32_t n, int32_t n_pre);
+hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
+                               hipStream_t s);
 // part -> res[p].node / best (count is copied in), then the chosen nodes'
 // victims [n_pre][max_victims], -1 padded (victims may be NULL).
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
@@ -105,9 +114,10 @@ struct StreamState {
 // Phase 1 (the preemptors on the loaded state, per-block partials and counts,
 // a tile of 32 at a time) and per preemptor k: k_preempt_seq (the blocks that
 // have to evaluate k again), k_preempt_seq_pick, k_preempt_apply.  full: the
-// A/B knob, every block evaluates every preemptor again.  Nothing synchronises.
+// A/B knob, every block evaluates every preemptor again.  plane: as for
+// launch_preempt, written once before the first preemptor.  Nothing synchronises.
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
-                                 int32_t max_victims, bool full, hipStream_t s);
+                                 int32_t max_victims, bool full, const uint64_t *plane, hipStream_t s);
 
 }  // namespace kh

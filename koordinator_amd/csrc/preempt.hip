@@ -18,6 +18,12 @@
 //                     writes ONE partial (the best candidate's verdict) per
 //                     preemptor.  No 128-bit key ever meets a global atomic.
 //   k_preempt_pick    one wave per preemptor over the workgroups' partials.
+//   k_preempt_numa    the NUMA mode's pre-pass: the NodeNUMAResource Filter of
+//                     every (preemptor, node) on the loaded NUMA rows, two bits
+//                     per pair (fails / fails unresolvably), written as one
+//                     ballot word per wave.  The plugin has no
+//                     PreFilterExtensions, so the verdict holds for the whole
+//                     call; the *_n kernels below are the walk reading it.
 //   k_preempt_victims one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
 //   k_preempt_blk / k_preempt_seq / k_preempt_seq_pick / k_preempt_apply
@@ -152,14 +158,24 @@ constexpr int EMIT_NONE = 0, EMIT_IDX = 1, EMIT_POS = 2;
 // listed pods are list[0, len).  EMIT_IDX: the victims' table indices go to
 // vout[0, vmax) in append order; EMIT_POS: their list positions.  OVL: on the
 // row without the gone pods and with the nominated pods of P's priority and
-// above, over the list without the gone positions.
-template <int EMIT, bool OVL>
+// above, over the list without the gone positions.  NUMA: NodeNUMAResource is
+// in the Filter; fcode is the frozen verdict of its Filter without
+// filterAmplifiedCPUs (NUMA_F_*, 0: passes), which moves with the row and is
+// part of every fit test here (of nr it reads cls, cnt and amp).
+constexpr uint32_t NUMA_F_FAIL = 1u, NUMA_F_UNRESOLVABLE = 2u;
+
+template <int EMIT, bool OVL, bool NUMA>
 __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
                                                               const NumaRowRS<1> &nr, const DevAsg *__restrict__ list,
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
-                                                              int32_t *vout, int32_t vmax, const NodeOverlay &ov) {
+                                                              int32_t *vout, int32_t vmax, const NodeOverlay &ov,
+                                                              uint32_t fcode) {
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
+  auto amp_ok = [&](const NV &x) {
+    if constexpr (NUMA) return !c.amp || amp_filter_ok(pod, x, nr);
+    return true;
+  };
   if (filter_status(c, pod, v, nr, classes, 0, 0u) & KOORDHIP_ST_STATIC_FAIL) {
     r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
     return r;
@@ -177,6 +193,26 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     }
     for (int32_t e = ov.head; e >= 0; e = ov.nom[e].next)
       if (ov.nom[e].prio >= pprio) apply_delta(w, ov.nom[e].pod, +1);
+  }
+  if constexpr (NUMA) {
+    if (fcode) {
+      // the first failing plugin in Filter order decides whether preemption might help
+      if ((fcode & NUMA_F_UNRESOLVABLE) && filter_status(c, pod, w, nr, classes, 0, 0u) == 0u && amp_ok(w)) {
+        r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
+        return r;
+      }
+      // no removal changes the verdict: UNFIT with a potential victim, NO_VICTIMS without
+      bool any = false;
+      for (int32_t k = 0; k < len && !any; k++) {
+        if constexpr (OVL) {
+          if (((k < 64 ? ov.g0 : ov.g1) >> (k & 63)) & 1ull) continue;
+        }
+        const DevAsg &a = list[k];
+        any = !((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota);
+      }
+      r.status = any ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
+      return r;
+    }
   }
   QuotaUsed q;
   int32_t pa[KOORDHIP_PREEMPT_PDBS];
@@ -214,7 +250,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     r.status = KOORDHIP_PREEMPT_NO_VICTIMS;
     return r;
   }
-  if (filter_status(c, pod, w, nr, classes, 0, 0u) != 0u) {
+  if (filter_status(c, pod, w, nr, classes, 0, 0u) != 0u || !amp_ok(w)) {
     r.status = KOORDHIP_PREEMPT_UNFIT;
     return r;
   }
@@ -231,7 +267,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       m &= m - 1;
       const DevAsg &a = list[k];
       move_pod(w, q, a, +1);
-      const bool fits = filter_status(c, pod, w, nr, classes, 0, 0u) == 0u;
+      const bool fits = filter_status(c, pod, w, nr, classes, 0, 0u) == 0u && amp_ok(w);
       if (!fits) move_pod(w, q, a, -1);
       bool over = false;
       if (pquota >= 0) {
@@ -278,14 +314,94 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
 // The dry run's envelope as the compiler sees it: only NodeResourcesFit,
 // LoadAware and the static filters can be in the Filter (launch_preempt refuses
 // the rest) and no Score is read, so with these masks the NodeNUMAResource and
-// Reservation halves of filter_status and their row fields fold away.
+// Reservation halves of filter_status and their row fields fold away.  NUMA:
+// the same masks (the NodeNUMAResource Filter arrives as preempt_node's fcode),
+// with amp kept for filterAmplifiedCPUs.
+template <bool NUMA>
 __device__ __forceinline__ DevCfg envelope(DevCfg c) {
   c.filt &= KOORDHIP_PLUGIN_FIT | KOORDHIP_PLUGIN_LOADAWARE | KOORDHIP_PLUGIN_NODE_STATIC;
   c.score = 0;
   c.resv = 0;
   c.zones = 0;
-  c.amp = 0;
+  if constexpr (!NUMA) c.amp = 0;
   return c;
+}
+
+// The walk's NUMA row.  Without NUMA: what load_numa leaves under the envelope
+// (nothing is read).  With it: the three fields filterAmplifiedCPUs reads.
+template <bool NUMA>
+__device__ __forceinline__ void load_walk_numa(NumaRowRS<1> &nr, const DevCfg &c, const DevNodes &d, int32_t i,
+                                               const Need &all) {
+  load_numa<true>(nr, d, i, all);
+  if constexpr (NUMA) {
+    if (c.amp) {
+      nr.cls = d.nu.node_cls[i];
+      nr.amp = d.nu.amp[i];
+      nr.cnt = d.nu.cnt[i];
+    }
+  }
+}
+
+// The frozen verdicts of one call: plane[p][2][nw] u64, bit b of word w is node
+// 64 w + b; [p][0]: the NodeNUMAResource Filter fails, [p][1]: with an
+// UnschedulableAndUnresolvable reason.
+struct NumaPlane {
+  const uint64_t *w;  // preemptor 0's words
+  int32_t nw;         // words per row: ceil(n / 64)
+};
+
+// node i's code for preemptor p (the wave reads one word per row)
+__device__ __forceinline__ uint32_t plane_code(const NumaPlane &pl, int32_t p, int32_t i) {
+  const int32_t word = i >> 6;
+  if (word >= pl.nw) return 0u;
+  const uint64_t *row = pl.w + (size_t)p * 2 * pl.nw + word;
+  const uint32_t b = (uint32_t)i & 63u;
+  return (uint32_t)((row[0] >> b) & 1ull) * NUMA_F_FAIL | (uint32_t)((row[pl.nw] >> b) & 1ull) * NUMA_F_UNRESOLVABLE;
+}
+
+// ---------------------------------------------------------------------------
+// k_preempt_numa
+
+// One thread per node, 32 preemptors per workgroup: numa_reason without the
+// amplification exit on the loaded NUMA row.  A preemptor the plugin does not
+// act on (no cpuset, no topology-policy node in the snapshot) gets zero words.
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_numa(DevCfg cfg, DevNodes d,
+                                                                  const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                  uint64_t *__restrict__ plane, int32_t nw) {
+  DevCfg c = cfg;
+  c.amp = 0;  // filterAmplifiedCPUs reads the row: it is the walk's
+  __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
+  const int t = threadIdx.x, lane = __lane_id();
+  const int32_t p0 = (int32_t)blockIdx.y * PRE_PT;
+  const int32_t np = min(PRE_PT, n_pre - p0);
+  const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
+  for (int32_t w = t; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
+  __syncthreads();
+  const DevPre *sp = reinterpret_cast<const DevPre *>(spw);
+  const int32_t i = (int32_t)blockIdx.x * PREEMPT_THREADS + t;
+  const bool live = i < d.n;
+  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and set no bit
+  const int32_t word = i >> 6;            // 256-node blocks are 64-aligned: a ballot is a plane word
+  Need all{};
+  all.numa = all.numa_masks = true;
+  all.zones = c.zones != 0;
+  NumaRow nr{};
+  load_numa<true>(nr, d, il, all);
+  const NV v{};  // read by the amplification exit only
+  for (int32_t q = 0; q < np; q++) {
+    const DevPod &pod = sp[q].pod;
+    uint64_t fail = 0, unres = 0;
+    if (numa_active(pod, c)) {  // wave-uniform
+      const uint32_t m = live ? numa_reason(c, pod, v, nr, d.nu.cls) : 0u;
+      fail = __ballot(m != 0u);
+      unres = __ballot((m & KOORDHIP_REASON_UNRESOLVABLE_MASK) != 0u);
+    }
+    if (lane == 0 && word < nw) {
+      uint64_t *row = plane + (size_t)(p0 + q) * 2 * nw + word;
+      row[0] = fail;
+      row[nw] = unres;
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -312,14 +428,15 @@ __device__ __forceinline__ void wave_best(koordhip_preempt_node &r, int32_t &bn)
 
 // BLK: the workgroup's counts go to bcnt [n_pre][gridDim.x][5] instead of
 // being summed into count (the sequential dry run replaces single blocks).
-template <bool BLK>
+// NUMA: pl holds the frozen verdicts of pre[0, n_pre).
+template <bool BLK, bool NUMA>
 __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
                                               const int32_t *__restrict__ off, const PdbAllowed &pdb,
                                               const DevPre *__restrict__ pre, int32_t n_pre,
                                               int32_t *__restrict__ count, PreemptPartial *__restrict__ part,
                                               koordhip_preempt_node *__restrict__ per_node,
-                                              int32_t *__restrict__ bcnt) {
-  const DevCfg c = envelope(cfg);
+                                              int32_t *__restrict__ bcnt, const NumaPlane &pl) {
+  const DevCfg c = envelope<NUMA>(cfg);
   __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
   __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_PT][PRE_WAVES];
@@ -338,13 +455,17 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
   const Need all = need_all(c);
   load_node(v, d, il, all, c);
   NumaRowRS<1> nr{};
-  load_numa<true>(nr, d, il, all);
+  load_walk_numa<NUMA>(nr, c, d, il, all);
   const int32_t lo = off[il];
   const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
   const DevAsg *list = tab + lo;
   for (int32_t q = 0; q < np; q++) {
     koordhip_preempt_node r{};
-    if (live) r = preempt_node<EMIT_NONE, false>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{});
+    uint32_t fcode = 0u;
+    if constexpr (NUMA) fcode = plane_code(pl, p0 + q, i);
+    if (live)
+      r = preempt_node<EMIT_NONE, false, NUMA>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{},
+                                                fcode);
     const int32_t st = live ? r.status : -1;
 #pragma unroll
     for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
@@ -388,7 +509,18 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNode
                                                              int32_t *__restrict__ count,
                                                              PreemptPartial *__restrict__ part,
                                                              koordhip_preempt_node *__restrict__ per_node) {
-  preempt_tiles<false>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr);
+  preempt_tiles<false, false>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, NumaPlane{});
+}
+
+// ... with NodeNUMAResource in the Filter, reading k_preempt_numa's plane
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                               const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                               const DevPre *__restrict__ pre, int32_t n_pre,
+                                                               int32_t *__restrict__ count,
+                                                               PreemptPartial *__restrict__ part,
+                                                               koordhip_preempt_node *__restrict__ per_node,
+                                                               NumaPlane pl) {
+  preempt_tiles<false, true>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
 }
 
 // Phase 1 of the sequential dry run: one tile of preemptors on the loaded
@@ -401,7 +533,19 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_blk(DevCfg cfg, Dev
                                                                  int32_t *__restrict__ bcnt,
                                                                  const StreamFlags *__restrict__ flags) {
   if (flags->pdb | flags->full) return;
-  preempt_tiles<true>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt);
+  preempt_tiles<true, false>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt, NumaPlane{});
+}
+
+// ... in the NUMA mode (pl: the tile's first preemptor's words)
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_blk_n(DevCfg cfg, DevNodes d,
+                                                                   const DevAsg *__restrict__ tab,
+                                                                   const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                                   const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                   PreemptPartial *__restrict__ part,
+                                                                   int32_t *__restrict__ bcnt,
+                                                                   const StreamFlags *__restrict__ flags, NumaPlane pl) {
+  if (flags->pdb | flags->full) return;
+  preempt_tiles<true, true>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt, pl);
 }
 
 // one wave per preemptor over its nb partials
@@ -439,13 +583,15 @@ __global__ __launch_bounds__(64) void k_preempt_pick(const PreemptPartial *__res
   }
 }
 
-// one thread per preemptor: its chosen node again, writing the victims (vout is -1 filled by the caller)
-__global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                        const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                        const DevPre *__restrict__ pre, int32_t n_pre,
-                                                        const koordhip_preempt_result *__restrict__ res,
-                                                        int32_t *__restrict__ vout, int32_t vmax) {
-  const DevCfg c = envelope(cfg);
+// one thread per preemptor: its chosen node again, writing the victims (vout is -1 filled by the caller).
+// NUMA: a chosen node is a CANDIDATE, so its frozen verdict is "passes" and only filterAmplifiedCPUs is left.
+template <bool NUMA>
+__device__ __forceinline__ void preempt_victims(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
+                                                const int32_t *__restrict__ off, const PdbAllowed &pdb,
+                                                const DevPre *__restrict__ pre, int32_t n_pre,
+                                                const koordhip_preempt_result *__restrict__ res,
+                                                int32_t *__restrict__ vout, int32_t vmax) {
+  const DevCfg c = envelope<NUMA>(cfg);
   const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
   if (p >= n_pre) return;
   const int32_t i = res[p].node;
@@ -454,12 +600,28 @@ __global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, 
   const Need all = need_all(c);
   load_node(v, d, i, all, c);
   NumaRowRS<1> nr{};
-  load_numa<true>(nr, d, i, all);
+  load_walk_numa<NUMA>(nr, c, d, i, all);
   const int32_t lo = off[i];
   const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
   const DevPre P = pre[p];
-  (void)preempt_node<EMIT_IDX, false>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
-                                         NodeOverlay{});
+  (void)preempt_node<EMIT_IDX, false, NUMA>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
+                                            NodeOverlay{}, 0u);
+}
+
+__global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                        const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                        const DevPre *__restrict__ pre, int32_t n_pre,
+                                                        const koordhip_preempt_result *__restrict__ res,
+                                                        int32_t *__restrict__ vout, int32_t vmax) {
+  preempt_victims<false>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
+}
+
+__global__ __launch_bounds__(64) void k_preempt_victims_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                          const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                          const DevPre *__restrict__ pre, int32_t n_pre,
+                                                          const koordhip_preempt_result *__restrict__ res,
+                                                          int32_t *__restrict__ vout, int32_t vmax) {
+  preempt_victims<true>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
 }
 
 // ---------------------------------------------------------------------------
@@ -495,10 +657,10 @@ __device__ __forceinline__ DevPre stream_pre(const DevPre *__restrict__ pre, con
 // Block b evaluates preemptor k again iff its rows / lists changed, the
 // budgets changed or k's quota was freed; a block none of this holds for keeps
 // the partial and the counts phase 1 wrote (they depend on nothing else).
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                                 const int32_t *__restrict__ off,
-                                                                 const DevPre *__restrict__ pre, int32_t k,
-                                                                 StreamState st) {
+template <bool NUMA>
+__device__ __forceinline__ void preempt_seq(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
+                                            const int32_t *__restrict__ off, const DevPre *__restrict__ pre, int32_t k,
+                                            const StreamState &st, const NumaPlane &pl) {
   const int t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
   const int32_t b = (int32_t)blockIdx.x, nb = (int32_t)gridDim.x;
   const StreamFlags fl = *st.flags;
@@ -507,7 +669,7 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, Dev
     return;
   }
   if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.stats->block_recomputes), 1ull);
-  const DevCfg c = envelope(cfg);
+  const DevCfg c = envelope<NUMA>(cfg);
   __shared__ int32_t scnt[KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_WAVES];
   if (t < KOORDHIP_PREEMPT_STATUSES) scnt[t] = 0;
@@ -521,12 +683,15 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, Dev
   const Need all = need_all(c);
   load_node(v, d, il, all, c);
   NumaRowRS<1> nr{};
-  load_numa<true>(nr, d, il, all);
+  load_walk_numa<NUMA>(nr, c, d, il, all);
   const int32_t lo = off[il];
   const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
   koordhip_preempt_node r{};
+  uint32_t fcode = 0u;
+  if constexpr (NUMA) fcode = plane_code(pl, k, i);
   if (live)
-    r = preempt_node<EMIT_NONE, true>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, nullptr, 0, overlay_of(st, il));
+    r = preempt_node<EMIT_NONE, true, NUMA>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, nullptr, 0, overlay_of(st, il),
+                                            fcode);
   const int32_t s0 = live ? r.status : -1;
 #pragma unroll
   for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
@@ -552,6 +717,21 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, Dev
     st.part[(size_t)k * nb + b] = x;
   }
   if (t < KOORDHIP_PREEMPT_STATUSES) st.bcnt[((size_t)k * nb + b) * KOORDHIP_PREEMPT_STATUSES + t] = scnt[t];
+}
+
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off,
+                                                                 const DevPre *__restrict__ pre, int32_t k,
+                                                                 StreamState st) {
+  preempt_seq<false>(cfg, d, tab, off, pre, k, st, NumaPlane{});
+}
+
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq_n(DevCfg cfg, DevNodes d,
+                                                                   const DevAsg *__restrict__ tab,
+                                                                   const int32_t *__restrict__ off,
+                                                                   const DevPre *__restrict__ pre, int32_t k,
+                                                                   StreamState st, NumaPlane pl) {
+  preempt_seq<true>(cfg, d, tab, off, pre, k, st, pl);
 }
 
 // one wave: preemptor k's nb partials and counts -> res[k]
@@ -588,10 +768,11 @@ __global__ __launch_bounds__(64) void k_preempt_seq_pick(int32_t nb, int32_t k, 
 
 // One wave: the chosen node of preemptor k again, its victims written out and
 // taken off the state every later preemptor sees.
-__global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                      const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
-                                                      int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
-  const DevCfg c = envelope(cfg);
+template <bool NUMA>
+__device__ __forceinline__ void preempt_apply(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
+                                              const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
+                                              int32_t n_pre, int32_t k, const StreamState &st, int32_t vmax) {
+  const DevCfg c = envelope<NUMA>(cfg);
   const int lane = threadIdx.x;
   const int32_t i = st.res[k].node;
   if (i < 0 || i >= d.n) return;
@@ -611,10 +792,10 @@ __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, co
     const Need all = need_all(c);
     load_node(v, d, i, all, c);
     NumaRowRS<1> nr{};
-    load_numa<true>(nr, d, i, all);
+    load_walk_numa<NUMA>(nr, c, d, i, all);
     PdbAllowed pdb = *st.pdb;
-    const koordhip_preempt_node r = preempt_node<EMIT_POS, true>(c, d.nu.cls, v, nr, list, len, pdb, P, st.vpos,
-                                                                 KOORDHIP_PREEMPT_NODE_PODS, overlay_of(st, i));
+    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA>(c, d.nu.cls, v, nr, list, len, pdb, P, st.vpos,
+                                                                       KOORDHIP_PREEMPT_NODE_PODS, overlay_of(st, i), 0u);
     const int32_t nv = r.status == KOORDHIP_PREEMPT_CANDIDATE ? min(r.n_victims, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
     uint64_t g0 = 0, g1 = 0;
     int64_t sum[KOORDHIP_PREEMPT_QRES] = {};
@@ -664,6 +845,18 @@ __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, co
   }
 }
 
+__global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                      const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
+                                                      int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
+  preempt_apply<false>(cfg, d, tab, off, pre, n_pre, k, st, vmax);
+}
+
+__global__ __launch_bounds__(64) void k_preempt_apply_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                        const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
+                                                        int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
+  preempt_apply<true>(cfg, d, tab, off, pre, n_pre, k, st, vmax);
+}
+
 // ---------------------------------------------------------------------------
 // host-side launch wrappers
 
@@ -687,37 +880,73 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
   return hipGetLastError();
 }
 
+size_t preempt_plane_words(int32_t n, int32_t n_pre) { return (size_t)std::max(n_pre, 0) * 2 * (((size_t)n + 63) / 64); }
+
+// NodeNUMAResource in the Filter needs the plane, Reservation is outside the envelope
+static bool preempt_profile_ok(const DevCfg &c, const uint64_t *plane) {
+  if (c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION)) return false;
+  return ((c.filt & KOORDHIP_PLUGIN_NUMA) != 0) == (plane != nullptr);
+}
+
+hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
+                               hipStream_t s) {
+  if (n_pre <= 0 || d.n <= 0) return hipSuccess;
+  if (!(c.filt & KOORDHIP_PLUGIN_NUMA) || !plane) return hipErrorInvalidValue;
+  const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_preempt_numa, grid, dim3(PREEMPT_THREADS), 0, s, c, d, pre, n_pre, plane, (d.n + 63) / 64);
+  return hipGetLastError();
+}
+
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, hipStream_t s) {
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (c.resv || (c.filt & (KOORDHIP_PLUGIN_NUMA | KOORDHIP_PLUGIN_RESERVATION))) return hipErrorInvalidValue;
+  if (!preempt_profile_ok(c, plane)) return hipErrorInvalidValue;
   if (per_node && n_pre != 1) return hipErrorInvalidValue;
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_preempt, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node);
+  if (plane)
+    hipLaunchKernelGGL(k_preempt_n, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part,
+                       per_node, NumaPlane{plane, (d.n + 63) / 64});
+  else
+    hipLaunchKernelGGL(k_preempt, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node);
   return hipGetLastError();
 }
 
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
-                                 int32_t max_victims, bool full, hipStream_t s) {
+                                 int32_t max_victims, bool full, const uint64_t *plane, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (c.resv || (c.filt & (KOORDHIP_PLUGIN_NUMA | KOORDHIP_PLUGIN_RESERVATION))) return hipErrorInvalidValue;
+  if (!preempt_profile_ok(c, plane)) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
+  const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
   fl.full = full ? 1 : 0;
   hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, s, pdb, fl, st);
   for (int32_t k = 0; k < n_pre; k++) {
     // phase 1 a tile ahead of its first preemptor, not all at once: the loaded state does not change, and a tile
     // launched after the budgets changed costs an empty kernel
-    if (k % PRE_PT == 0)
-      hipLaunchKernelGGL(k_preempt_blk, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
-                         std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
-                         st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags);
-    hipLaunchKernelGGL(k_preempt_seq, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st);
+    if (k % PRE_PT == 0) {
+      if (plane)
+        hipLaunchKernelGGL(k_preempt_blk_n, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
+                           std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
+                           st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags,
+                           NumaPlane{plane + (size_t)k * 2 * pl.nw, pl.nw});
+      else
+        hipLaunchKernelGGL(k_preempt_blk, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
+                           std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
+                           st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags);
+    }
+    if (plane)
+      hipLaunchKernelGGL(k_preempt_seq_n, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st, pl);
+    else
+      hipLaunchKernelGGL(k_preempt_seq, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st);
     hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), dim3(64), 0, s, nb, k, st);
-    hipLaunchKernelGGL(k_preempt_apply, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
+    if (plane)
+      hipLaunchKernelGGL(k_preempt_apply_n, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
+    else
+      hipLaunchKernelGGL(k_preempt_apply, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
   }
   return hipGetLastError();
 }
@@ -728,9 +957,14 @@ hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg 
                                int32_t max_victims, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
-  if (victims && max_victims > 0)
-    hipLaunchKernelGGL(k_preempt_victims, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res,
-                       victims, max_victims);
+  if (victims && max_victims > 0) {
+    if (c.filt & KOORDHIP_PLUGIN_NUMA)
+      hipLaunchKernelGGL(k_preempt_victims_n, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre,
+                         res, victims, max_victims);
+    else
+      hipLaunchKernelGGL(k_preempt_victims, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre,
+                         res, victims, max_victims);
+  }
   return hipGetLastError();
 }
 

@@ -366,6 +366,18 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_preempt_load_pods(self._ctx, a.ctypes.data, len(a),
                                                                 abi.ptr(pdb, C.c_int32), len(pdb)))
 
+    def preempt_set_mode(self, numa_frozen: bool = False, flags: int = None):
+        """numa_frozen: the dry-run calls accept NodeNUMAResource in the Filter,
+        with the plugin's verdict frozen for the call: victims' cpusets and
+        zone amounts are not freed and a nominated cpuset preemptor holds no
+        CPUs, as in the reference (include/koordhip.h).  The mode is the
+        context's; False restores the refusal.  flags: the raw
+        abi.PREEMPT_* word instead."""
+        if not hasattr(self.lib, "koordhip_preempt_set_mode"):
+            raise RuntimeError("this libkoordhip build has no koordhip_preempt_set_mode")
+        word = (abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) if flags is None else int(flags)
+        abi.check(self.lib, self.lib.koordhip_preempt_set_mode(self._ctx, word))
+
     def preempt(self, preemptors: np.ndarray, max_victims: int = 0):
         """SelectVictimsOnNode on every node and the candidate pick, per
         preemptor (abi.PREEMPTOR_DTYPE) against the current state: returns
