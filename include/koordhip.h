@@ -913,6 +913,12 @@ int koordhip_node_reasons_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const 
 
 #define KOORDHIP_ASG_NONPREEMPTIBLE 1u /* extension.IsPodNonPreemptible */
 #define KOORDHIP_ASG_IN_QUOTA 2u       /* quotaInfo.IsPodExist: the quota's used moves with the pod (plugin.go:302-305) */
+/* bits 8-11 of flags: the reservation slot of ITS NODE the pod is bound to (its
+ * reservation-allocated annotation), read in the KOORDHIP_PREEMPT_RESV mode
+ * only.  A field value of 0 means not bound. */
+#define KOORDHIP_ASG_RESV_SLOT(q) ((uint32_t)((q) + 1) << 8)
+#define KOORDHIP_ASG_RESV_SLOT_MASK (15u << 8)
+#define KOORDHIP_ASG_RESV_SLOT_OF(flags) (((flags) >> 8) & 15u) /* the field: slot + 1, 0 = not bound */
 
 typedef struct koordhip_assigned {
   koordhip_pod pod;
@@ -967,7 +973,10 @@ typedef struct koordhip_preempt_result {
  * the engine's).  The table does not depend on the node state: it stays until
  * the next call of this function or of load_snapshot.  KOORDHIP_EINVAL for a
  * node outside [0, n), more than KOORDHIP_PREEMPT_NODE_PODS pods on a node,
- * n_pdb above KOORDHIP_PREEMPT_PDBS, a pdb_mask bit at or above n_pdb. */
+ * n_pdb above KOORDHIP_PREEMPT_PDBS, a pdb_mask bit at or above n_pdb, a
+ * KOORDHIP_ASG_RESV_SLOT field above the loaded snapshot's resv_slots (ignored
+ * without reservation columns; whether the slot is present on the node is not
+ * checked). */
 int koordhip_preempt_load_pods(koordhip_ctx *ctx, const koordhip_assigned *a, int32_t n_assigned,
                                const int32_t *pdb_allowed /* [n_pdb] DisruptionsAllowed */, int32_t n_pdb);
 /* The dry run of n_pre preemptors, each on its own against the current state.
@@ -979,8 +988,8 @@ int koordhip_preempt_load_pods(koordhip_ctx *ctx, const koordhip_assigned *a, in
  * appends them, padded with -1; with max_victims below best.n_victims the
  * list is truncated.  Profiles whose Filter is NodeResourcesFit, LoadAware
  * and the static filters on the pipelined path; KOORDHIP_EINVAL for
- * NodeNUMAResource (unless koordhip_preempt_set_mode below accepted it) or
- * Reservation in the Filter, Reservation snapshots, sequential-cycle profiles,
+ * NodeNUMAResource, Reservation in the Filter or Reservation snapshots (each
+ * unless koordhip_preempt_set_mode below accepted it), sequential-cycle profiles,
  * reserve pods and an attached communicator; KOORDHIP_ESTATE without a
  * snapshot or a loaded table. */
 int koordhip_preempt(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
@@ -1021,10 +1030,66 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *
  * flags = 0 (the default) restores the refusal.  The mode belongs to the
  * context: it outlives load_snapshot and koordhip_preempt_load_pods, and it is
  * inert on a profile without NodeNUMAResource in the Filter.  KOORDHIP_EINVAL
- * for an unknown bit.  With the flag set still KOORDHIP_EINVAL: everything
+ * for an unknown bit (the mode then stays as it was).  With the flag set still KOORDHIP_EINVAL: everything
  * koordhip_preempt lists besides NodeNUMAResource, and a preemptor with
  * KOORDHIP_POD_NUMA_ERROR (a PreFilter error aborts the cycle: no PostFilter). */
 #define KOORDHIP_PREEMPT_NUMA_FROZEN 1u
+/* ---- the dry run under Reservation (additive to ABI 15: detect it by the flag's acceptance)
+ * KOORDHIP_PREEMPT_RESV lets koordhip_preempt and koordhip_preempt_node_verdicts
+ * accept Reservation columns and the Reservation Filter on the pipelined path
+ * (at most KOORDHIP_RESV_SLOTS reservations per node, no sequential-cycle
+ * snapshot).  Unlike NodeNUMAResource the plugin has PreFilterExtensions
+ * (reservation/plugin.go:250-323): its AddPod / RemovePod keep
+ * preemptible[node] and preemptibleInRRs[node][reservation UID], and
+ * filterWithReservations / fitsNode read both (:373-494).  The walk keeps that
+ * state per (preemptor P, node):
+ *   start row   the loaded row after the cycle's Reservation restore for P
+ *               (the PostFilter runs on the NodeInfo BeforePreFilter restored).
+ *   frozen      the reservation slots (Allocatable, Allocated, assigned count,
+ *               policy, class) and nodeRState.podRequested, the clone taken
+ *               before the matched restore (transformer.go:129); a node without
+ *               a matched / unmatched-with-pods reservation has none (0).
+ *   moving      over cpu, memory, ephemeral-storage, batch-cpu, batch-memory:
+ *               RemovePod of a listed pod with a non-zero request adds its
+ *               requests to Pn (not bound) or Pr[q] (bound to slot q, see
+ *               KOORDHIP_ASG_RESV_SLOT); AddPod of a pod that is not bound
+ *               subtracts from Pn, floored at 0.  AddPod of a BOUND pod is
+ *               restated literally (:278-286): Pr[q] is deleted when Pr[q] -
+ *               requests is zero in every resource and otherwise KEEPS ITS OLD
+ *               VALUE (the reference never stores the difference; no reference
+ *               table pins the partial add-back: parity unpinned, followed
+ *               literally).  An entry is present iff some resource is
+ *               non-zero.  Pods without requests move the row only.
+ * Every "does P fit row w" is the test of the default mode (in the NUMA mode
+ * with F and A(w)) and the Reservation Filter: without a matched reservation a
+ * pod with KOORDHIP_POD_RESV_AFFINITY fails, otherwise, if Pn or some Pr[q] is
+ * present, fitsNode(nil, preemptible = Pn) decides (ErrReasonPreemptionFailed);
+ * with matched reservations fitsNode per slot q with preemptible = Pr[q] + Pn
+ * and rRemained from the unmodified Allocated: a Default slot is insufficient
+ * only if Pr[q] or Pn is present and fitsNode fails, an Aligned slot passes the
+ * node if fitsNode passes, a Restricted one if also podRequests <= max(0,
+ * Allocatable - a) over its resource names, a = max(0, Allocated - Pr[q]) with
+ * Pr[q] present, else Allocated (:420-432); the node fails iff no Aligned /
+ * Restricted slot passed and one policy group is non-empty and wholly
+ * insufficient (:434-437).  UNRESOLVABLE as koordhip_diagnose_reasons counts
+ * it: on the start row the first failing plugin holds one of
+ * KOORDHIP_REASON_UNRESOLVABLE_MASK's reasons, now RESV_AFFINITY too.
+ *
+ * Named deviation: reserve pods are NOT listed in this mode (AddPod / RemovePod
+ * skip them at :255,293, but NodeInfo.RemovePod would still move the restored
+ * row): they are never potential victims.  Still KOORDHIP_EINVAL: reserve and
+ * operating-mode preemptors; koordhip_preempt_stream on Reservation state, flag
+ * or not (earlier victims would have to leave the reservations' Allocated);
+ * with NodeNUMAResource in the Filter the flag without
+ * KOORDHIP_PREEMPT_NUMA_FROZEN, and both flags on a snapshot loaded with
+ * resv_cpus (the frozen verdict does not model the restore of reserved CPUs).
+ * The flag is inert on a context without Reservation state, with one
+ * exception that koordhip_preempt_set_mode itself answers: on a profile with
+ * NodeNUMAResource in the Filter and WITHOUT the Reservation plugin the word
+ * is live (it decides the NUMA refusal), and a word with this bit is
+ * KOORDHIP_EINVAL like an unknown bit and leaves the mode as it was: such a
+ * context can never hold Reservation state. */
+#define KOORDHIP_PREEMPT_RESV 2u
 int koordhip_preempt_set_mode(koordhip_ctx *ctx, uint32_t flags);
 
 /* ---- sequential preemption dry run (additive to ABI 15: detect it by the symbol)

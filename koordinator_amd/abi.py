@@ -325,9 +325,18 @@ def first_reasons_ext(mask):
 # koordhip_preemptor (208), koordhip_preempt_node (32) and koordhip_preempt_result (56)
 PREEMPT_QRES, PREEMPT_PDBS, PREEMPT_NODE_PODS = 4, 8, 128
 ASG_NONPREEMPTIBLE, ASG_IN_QUOTA = 1, 2
+ASG_RESV_SLOT_SHIFT, ASG_RESV_SLOT_MASK = 8, 15 << 8   # flags bits 8-11: slot + 1 of the node's reservation the pod is bound to
+
+
+def asg_resv_slot(q: int) -> int:
+    """KOORDHIP_ASG_RESV_SLOT(q): the koordhip_assigned.flags field of a pod bound to reservation slot q of its node."""
+    return (q + 1) << ASG_RESV_SLOT_SHIFT
+
+
 PREEMPT_CANDIDATE, PREEMPT_NO_VICTIMS, PREEMPT_UNFIT, PREEMPT_ERROR, PREEMPT_UNRESOLVABLE = range(5)
 PREEMPT_STATUSES = 5
 PREEMPT_NUMA_FROZEN = 1   # koordhip_preempt_set_mode: NodeNUMAResource in the Filter, its verdict frozen for the call
+PREEMPT_RESV = 2          # ... Reservation state: the walk keeps the plugin's AddPod / RemovePod state
 ASSIGNED_DTYPE = np.dtype([
     ("pod", POD_DTYPE), ("node", "<i4"), ("priority", "<i4"), ("start_time", "<i8"), ("quota", "<i4"),
     ("flags", "<u4"), ("pdb_mask", "<u4"), ("reserved", "<u4"), ("qreq", "<i8", (PREEMPT_QRES,)),

@@ -3643,8 +3643,16 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: assigned pod " + std::to_string(j) +
                                        " has a pdb_mask bit at or above n_pdb");
     if (s.quota < 0) return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: an assigned pod's quota id is >= 0");
-    if (s.flags & ~(KOORDHIP_ASG_NONPREEMPTIBLE | KOORDHIP_ASG_IN_QUOTA))
+    if (s.flags & ~(KOORDHIP_ASG_NONPREEMPTIBLE | KOORDHIP_ASG_IN_QUOTA | KOORDHIP_ASG_RESV_SLOT_MASK))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: unknown koordhip_assigned.flags bit");
+    // the reservation slot the pod is bound to: read only with reservation columns (whether the slot is present on
+    // the node is not checked: the reference keys the state by UID and does not care either)
+    uint32_t flags = s.flags;
+    if (!c->dc.resv)
+      flags &= ~KOORDHIP_ASG_RESV_SLOT_MASK;
+    else if ((int32_t)KOORDHIP_ASG_RESV_SLOT_OF(flags) > std::max(c->dc.resv_slots, 1))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: assigned pod " + std::to_string(j) +
+                                       " is bound to a reservation slot past the snapshot's resv_slots");
     kh::DevAsg &o = raw[j];
     std::memset(&o, 0, sizeof(o));
     o.pod = hp[j];
@@ -3656,7 +3664,7 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
     }
     o.prio = s.priority;
     o.quota = s.quota;
-    o.flags = s.flags;
+    o.flags = flags;
     o.pdb_mask = s.pdb_mask;
     o.idx = j;
     o.node = s.node;
@@ -3679,7 +3687,15 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
 
 int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
-  if (flags & ~KOORDHIP_PREEMPT_NUMA_FROZEN) return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: unknown flag bit");
+  if (flags & ~(KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV))
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: unknown flag bit");
+  // Where NodeNUMAResource is in the Filter the word decides what the dry-run calls accept, so a bit the profile
+  // has no plugin for is refused like an unknown one (a host that sets KOORDHIP_PREEMPT_RESV there expects
+  // Reservation state the context can never hold).  On a profile without that plugin both bits are inert.
+  if ((flags & KOORDHIP_PREEMPT_RESV) && (c->dc.filt & KOORDHIP_PLUGIN_NUMA) &&
+      !((c->dc.filt | c->dc.score) & KOORDHIP_PLUGIN_RESERVATION))
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: KOORDHIP_PREEMPT_RESV on a profile with NodeNUMAResource "
+                                 "in the Filter and without the Reservation plugin");
   c->pre_mode = flags;
   return 0;
 }
@@ -3687,6 +3703,15 @@ int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
 // NodeNUMAResource is in the Filter and the host accepted the frozen verdict
 static bool preempt_numa_mode(const koordhip_ctx *c) {
   return (c->pre_mode & KOORDHIP_PREEMPT_NUMA_FROZEN) && (c->dc.filt & KOORDHIP_PLUGIN_NUMA);
+}
+
+// The context has Reservation state (the Filter plugin or reservation columns) ...
+static bool preempt_resv_state(const koordhip_ctx *c) {
+  return c->dc.resv || (c->dc.filt & KOORDHIP_PLUGIN_RESERVATION);
+}
+// ... and the host accepted the walk that keeps the plugin's AddPod / RemovePod state: its slots per row, else 0
+static int preempt_resv_rs(const koordhip_ctx *c) {
+  return (c->pre_mode & KOORDHIP_PREEMPT_RESV) && preempt_resv_state(c) ? kh::preempt_resv_slots(c->dc) : 0;
 }
 
 // The NUMA mode's pre-pass for the uploaded preemptors; *plane stays NULL outside the mode.
@@ -3701,8 +3726,8 @@ static int preempt_plane(koordhip_ctx *c, int32_t n_pre, const uint64_t **plane)
   return 0;
 }
 
-// The checks the two dry-run calls share, and the preemptors' upload.
-static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre) {
+// The checks the dry-run calls share, and the preemptors' upload (stream: koordhip_preempt_stream asks).
+static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, bool stream = false) {
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (!c->pre_loaded)
     return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
@@ -3714,9 +3739,19 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with NodeNUMAResource in the Filter (it has no "
                                  "PreFilterExtensions: its state does not move in a dry run) unless "
                                  "koordhip_preempt_set_mode(KOORDHIP_PREEMPT_NUMA_FROZEN) accepted that");
-  if (c->dc.resv || (c->dc.filt & KOORDHIP_PLUGIN_RESERVATION))
-    return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
-                                 "not kept)");
+  if (preempt_resv_state(c)) {
+    if (stream)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not with Reservation plugin state, with or without "
+                                   "KOORDHIP_PREEMPT_RESV (earlier preemptors' victims would have to leave the "
+                                   "reservations' Allocated and assigned counts)");
+    if (!preempt_resv_rs(c))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
+                                   "not kept) unless koordhip_preempt_set_mode(KOORDHIP_PREEMPT_RESV) asked for it");
+    if (preempt_numa_mode(c) && c->dc.resv_cpus)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_NUMA_FROZEN with KOORDHIP_PREEMPT_RESV not on a "
+                                   "snapshot whose reservations hold CPUs (resv_cpus: the frozen NUMA verdict does not "
+                                   "model their restore)");
+  }
   if (c->comm || c->group || c->world > 1) return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with a communicator attached");
   std::vector<koordhip_pod> pods((size_t)n_pre);
   for (int32_t p = 0; p < n_pre; p++) {
@@ -3788,9 +3823,10 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
   if (int e = preempt_plane(c, n_pre, &plane)) return e;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, cb, c->stream));
   if (nv) HIP_TRY(hipMemsetAsync(d_vic, 0xFF, vb, c->stream));
-  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, plane, c->stream));
+  const int rs = preempt_resv_rs(c);
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, plane, rs, c->stream));
   HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, d_res, d_vic, max_victims,
-                                  c->stream));
+                                  rs, c->stream));
   HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, d_vic, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3804,7 +3840,7 @@ int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int3
   static_assert(sizeof(koordhip_preempt_stream_stats) == 24, "stream stats");
   if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
-  if (int e = preempt_ready(c, pre, n_pre)) return e;
+  if (int e = preempt_ready(c, pre, n_pre, true)) return e;
   if (stats) *stats = koordhip_preempt_stream_stats{};
   if (n_pre == 0) return 0;
   const int32_t n = c->n;
@@ -3894,7 +3930,8 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pr
   HIP_TRY(kh::launch_preempt(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
                              kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
                              static_cast<const kh::DevPre *>(c->d_pre_in), 1, reinterpret_cast<int32_t *>(base),
-                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, plane, c->stream));
+                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, plane, preempt_resv_rs(c),
+                             c->stream));
   HIP_TRY(hipMemcpyAsync(per_node, d_ver, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;

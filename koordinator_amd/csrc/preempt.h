@@ -57,9 +57,14 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
 // node's verdict.  plane: NULL, or with NodeNUMAResource in the Filter the
 // words launch_preempt_numa wrote for these preemptors (the walk then reads the
 // plugin's verdict there and evaluates filterAmplifiedCPUs on every row).
+// rs: 0, or with Reservation state (KOORDHIP_PREEMPT_RESV) preempt_resv_slots(c):
+// the walk then starts from the restored row and keeps the plugin's AddPod /
+// RemovePod state; DevAsg::flags bits 8-11 name the slot a listed pod is bound to.
+int preempt_resv_slots(const DevCfg &c);
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, hipStream_t s);
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, int rs,
+                          hipStream_t s);
 // The frozen NUMA verdict plane of pre[0, n_pre): plane [n_pre][2][ceil(n / 64)]
 // u64 (preempt_plane_words), bit b of word w is node 64 w + b; [p][0]: the
 // NodeNUMAResource Filter without filterAmplifiedCPUs fails on the loaded NUMA
@@ -72,7 +77,7 @@ hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre 
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, hipStream_t s);
+                               int32_t max_victims, int rs, hipStream_t s);
 
 // ---- the sequential dry run (koordhip_preempt_stream) ----------------------
 // Preemptor k is answered on the state the preemptors before it left: their

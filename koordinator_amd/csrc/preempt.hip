@@ -26,6 +26,13 @@
 //                     call; the *_n kernels below are the walk reading it.
 //   k_preempt_victims one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
+//   k_preempt_r / k_preempt_victims_r <NUMA, RS>
+//                     the same two with Reservation state (KOORDHIP_PREEMPT_RESV):
+//                     the walk starts from the row after the cycle's restore for
+//                     the preemptor and keeps the plugin's AddPod / RemovePod
+//                     state (preemptible, preemptibleInRRs: resv.hpp ResvPre)
+//                     per (preemptor, node) in registers; RS = 1 or
+//                     KOORDHIP_RESV_SLOTS reservation slots per node.
 //   k_preempt_blk / k_preempt_seq / k_preempt_seq_pick / k_preempt_apply
 //                     the sequential dry run (koordhip_preempt_stream): the
 //                     preemptors in input order, each on the state the earlier
@@ -162,26 +169,77 @@ constexpr int EMIT_NONE = 0, EMIT_IDX = 1, EMIT_POS = 2;
 // in the Filter; fcode is the frozen verdict of its Filter without
 // filterAmplifiedCPUs (NUMA_F_*, 0: passes), which moves with the row and is
 // part of every fit test here (of nr it reads cls, cnt and amp).
+//
+// RS > 0 (KOORDHIP_PREEMPT_RESV): the context has Reservation state, nr holds
+// the node's RS reservation slots.  The walk starts from the row after the
+// cycle's restore for P (the reference's PostFilter runs on the NodeInfo
+// BeforePreFilter restored), the slots and nodeRState.podRequested stay as they
+// are and every move of a listed pod also moves the plugin's AddPod /
+// RemovePod state (resv.hpp ResvPre), which filterWithReservations reads in
+// every fit test.  Not with OVL: the stream refuses Reservation state.
 constexpr uint32_t NUMA_F_FAIL = 1u, NUMA_F_UNRESOLVABLE = 2u;
 
-template <int EMIT, bool OVL, bool NUMA>
+template <int RS>
+using WalkRow = NumaRowRS<(RS > 0 ? RS : 1)>;
+
+// the reservation slot of its node a listed pod is bound to, -1: none
+__device__ __forceinline__ int asg_slot(const DevAsg &a) { return (int)((a.flags >> 8) & 15u) - 1; }
+
+// some pod of the list is a potential victim of P
+template <bool OVL>
+__device__ __forceinline__ bool any_potential(const DevAsg *__restrict__ list, int32_t len, const NodeOverlay &ov,
+                                              int32_t pprio, int32_t pquota) {
+  bool any = false;
+  for (int32_t k = 0; k < len && !any; k++) {
+    if constexpr (OVL) {
+      if (((k < 64 ? ov.g0 : ov.g1) >> (k & 63)) & 1ull) continue;
+    }
+    const DevAsg &a = list[k];
+    any = !((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota);
+  }
+  return any;
+}
+
+template <int EMIT, bool OVL, bool NUMA, int RS = 0>
 __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
-                                                              const NumaRowRS<1> &nr, const DevAsg *__restrict__ list,
+                                                              const WalkRow<RS> &nr, const DevAsg *__restrict__ list,
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
                                                               int32_t *vout, int32_t vmax, const NodeOverlay &ov,
                                                               uint32_t fcode) {
+  static_assert(!(OVL && RS > 0), "the sequential dry run holds no Reservation state");
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
   auto amp_ok = [&](const NV &x) {
     if constexpr (NUMA) return !c.amp || amp_filter_ok(pod, x, nr);
     return true;
   };
-  if (filter_status(c, pod, v, nr, classes, 0, 0u) & KOORDHIP_ST_STATIC_FAIL) {
+  // the Filter without the Reservation plugin (which reads the walk's state: resv_ok below)
+  auto base_status = [&](const NV &x) {
+    if constexpr (RS > 0) {
+      DevCfg cb = c;
+      cb.filt &= ~(uint32_t)KOORDHIP_PLUGIN_RESERVATION;
+      return filter_status(cb, pod, x, nr, classes, 0, 0u);
+    } else {
+      return filter_status(c, pod, x, nr, classes, 0, 0u);
+    }
+  };
+  if (base_status(v) & KOORDHIP_ST_STATIC_FAIL) {
     r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
     return r;
   }
   const int32_t pprio = P.prio, pquota = P.quota;
   NV w = v;
+  int nmatch = 0;
+  uint32_t mm = 0u;
+  ResvPre<(RS > 0 ? RS : 1)> rp;
+  if constexpr (RS > 0) {
+    if (c.resv) nmatch = resv_restore(w, nr, pod, mm);
+    resv_pre_init(rp, w, nr, pod, mm);
+  }
+  auto resv_ok = [&](const NV &x) {
+    if constexpr (RS > 0) return !(c.filt & KOORDHIP_PLUGIN_RESERVATION) || resv_filter_pre(pod, x, v, nr, mm, nmatch, rp);
+    return true;
+  };
   if constexpr (OVL) {
     for (int h = 0; h < 2; h++) {
       uint64_t g = h ? ov.g1 : ov.g0;
@@ -197,23 +255,30 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   if constexpr (NUMA) {
     if (fcode) {
       // the first failing plugin in Filter order decides whether preemption might help
-      if ((fcode & NUMA_F_UNRESOLVABLE) && filter_status(c, pod, w, nr, classes, 0, 0u) == 0u && amp_ok(w)) {
+      if ((fcode & NUMA_F_UNRESOLVABLE) && base_status(w) == 0u && amp_ok(w)) {
         r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
         return r;
       }
       // no removal changes the verdict: UNFIT with a potential victim, NO_VICTIMS without
-      bool any = false;
-      for (int32_t k = 0; k < len && !any; k++) {
-        if constexpr (OVL) {
-          if (((k < 64 ? ov.g0 : ov.g1) >> (k & 63)) & 1ull) continue;
-        }
-        const DevAsg &a = list[k];
-        any = !((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota);
-      }
-      r.status = any ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
+      r.status = any_potential<OVL>(list, len, ov, pprio, pquota) ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
       return r;
     }
   }
+  if constexpr (RS > 0) {
+    // a required reservation affinity without a matched reservation (plugin.go:378-381) fails whatever is removed;
+    // as the first failing plugin of the start row it is unresolvable
+    if ((c.filt & KOORDHIP_PLUGIN_RESERVATION) && nmatch == 0 && (pod.flags & KOORDHIP_POD_RESV_AFFINITY)) {
+      if (base_status(w) == 0u && amp_ok(w))
+        r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
+      else
+        r.status = any_potential<OVL>(list, len, ov, pprio, pquota) ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
+      return r;
+    }
+  }
+  auto move = [&](QuotaUsed &qu, const DevAsg &a, int sign) {
+    move_pod(w, qu, a, sign);
+    if constexpr (RS > 0) resv_pre_move(rp, a.pod, asg_slot(a), sign);
+  };
   QuotaUsed q;
   int32_t pa[KOORDHIP_PREEMPT_PDBS];
 #pragma unroll
@@ -228,7 +293,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     }
     const DevAsg &a = list[k];
     if ((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota) continue;
-    move_pod(w, q, a, -1);
+    move(q, a, -1);
     const uint32_t pm = a.pdb_mask;
     bool bad = false;
 #pragma unroll
@@ -250,7 +315,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     r.status = KOORDHIP_PREEMPT_NO_VICTIMS;
     return r;
   }
-  if (filter_status(c, pod, w, nr, classes, 0, 0u) != 0u || !amp_ok(w)) {
+  if (base_status(w) != 0u || !amp_ok(w) || !resv_ok(w)) {
     r.status = KOORDHIP_PREEMPT_UNFIT;
     return r;
   }
@@ -266,9 +331,9 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       const int32_t k = (int32_t)__ffsll((unsigned long long)m) - 1 + ((g & 1) ? 64 : 0);
       m &= m - 1;
       const DevAsg &a = list[k];
-      move_pod(w, q, a, +1);
-      const bool fits = filter_status(c, pod, w, nr, classes, 0, 0u) == 0u && amp_ok(w);
-      if (!fits) move_pod(w, q, a, -1);
+      move(q, a, +1);
+      const bool fits = base_status(w) == 0u && amp_ok(w) && resv_ok(w);
+      if (!fits) move(q, a, -1);
       bool over = false;
       if (pquota >= 0) {
 #pragma unroll
@@ -281,7 +346,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         return e;
       }
       if (fits && !over) continue;  // reprieved
-      if (over) move_pod(w, q, a, -1);
+      if (over) move(q, a, -1);
       if (!fits && violating) npdb++;
       const int32_t ap = a.prio;
       const int64_t as = a.start;
@@ -316,12 +381,14 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
 // the rest) and no Score is read, so with these masks the NodeNUMAResource and
 // Reservation halves of filter_status and their row fields fold away.  NUMA:
 // the same masks (the NodeNUMAResource Filter arrives as preempt_node's fcode),
-// with amp kept for filterAmplifiedCPUs.
-template <bool NUMA>
+// with amp kept for filterAmplifiedCPUs.  RS > 0: the Reservation Filter bit
+// and resv stay (the restore and the walk's own filterWithReservations).
+template <bool NUMA, int RS = 0>
 __device__ __forceinline__ DevCfg envelope(DevCfg c) {
-  c.filt &= KOORDHIP_PLUGIN_FIT | KOORDHIP_PLUGIN_LOADAWARE | KOORDHIP_PLUGIN_NODE_STATIC;
+  c.filt &= KOORDHIP_PLUGIN_FIT | KOORDHIP_PLUGIN_LOADAWARE | KOORDHIP_PLUGIN_NODE_STATIC |
+            (RS > 0 ? KOORDHIP_PLUGIN_RESERVATION : 0u);
   c.score = 0;
-  c.resv = 0;
+  if constexpr (RS == 0) c.resv = 0;
   c.zones = 0;
   if constexpr (!NUMA) c.amp = 0;
   return c;
@@ -329,8 +396,9 @@ __device__ __forceinline__ DevCfg envelope(DevCfg c) {
 
 // The walk's NUMA row.  Without NUMA: what load_numa leaves under the envelope
 // (nothing is read).  With it: the three fields filterAmplifiedCPUs reads.
-template <bool NUMA>
-__device__ __forceinline__ void load_walk_numa(NumaRowRS<1> &nr, const DevCfg &c, const DevNodes &d, int32_t i,
+// RS > 0: and the node's reservation slots.
+template <bool NUMA, int RS = 0>
+__device__ __forceinline__ void load_walk_numa(WalkRow<RS> &nr, const DevCfg &c, const DevNodes &d, int32_t i,
                                                const Need &all) {
   load_numa<true>(nr, d, i, all);
   if constexpr (NUMA) {
@@ -339,6 +407,9 @@ __device__ __forceinline__ void load_walk_numa(NumaRowRS<1> &nr, const DevCfg &c
       nr.amp = d.nu.amp[i];
       nr.cnt = d.nu.cnt[i];
     }
+  }
+  if constexpr (RS > 0) {
+    if (c.resv) load_resv(nr, d.rv, i);
   }
 }
 
@@ -428,15 +499,15 @@ __device__ __forceinline__ void wave_best(koordhip_preempt_node &r, int32_t &bn)
 
 // BLK: the workgroup's counts go to bcnt [n_pre][gridDim.x][5] instead of
 // being summed into count (the sequential dry run replaces single blocks).
-// NUMA: pl holds the frozen verdicts of pre[0, n_pre).
-template <bool BLK, bool NUMA>
+// NUMA: pl holds the frozen verdicts of pre[0, n_pre).  RS: preempt_node's.
+template <bool BLK, bool NUMA, int RS = 0>
 __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
                                               const int32_t *__restrict__ off, const PdbAllowed &pdb,
                                               const DevPre *__restrict__ pre, int32_t n_pre,
                                               int32_t *__restrict__ count, PreemptPartial *__restrict__ part,
                                               koordhip_preempt_node *__restrict__ per_node,
                                               int32_t *__restrict__ bcnt, const NumaPlane &pl) {
-  const DevCfg c = envelope<NUMA>(cfg);
+  const DevCfg c = envelope<NUMA, RS>(cfg);
   __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
   __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_PT][PRE_WAVES];
@@ -454,8 +525,8 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
   NV v{};
   const Need all = need_all(c);
   load_node(v, d, il, all, c);
-  NumaRowRS<1> nr{};
-  load_walk_numa<NUMA>(nr, c, d, il, all);
+  WalkRow<RS> nr{};
+  load_walk_numa<NUMA, RS>(nr, c, d, il, all);
   const int32_t lo = off[il];
   const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
   const DevAsg *list = tab + lo;
@@ -464,8 +535,8 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
     uint32_t fcode = 0u;
     if constexpr (NUMA) fcode = plane_code(pl, p0 + q, i);
     if (live)
-      r = preempt_node<EMIT_NONE, false, NUMA>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{},
-                                                fcode);
+      r = preempt_node<EMIT_NONE, false, NUMA, RS>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{},
+                                                    fcode);
     const int32_t st = live ? r.status : -1;
 #pragma unroll
     for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
@@ -521,6 +592,18 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_n(DevCfg cfg, DevNo
                                                                koordhip_preempt_node *__restrict__ per_node,
                                                                NumaPlane pl) {
   preempt_tiles<false, true>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
+}
+
+// ... with Reservation state (KOORDHIP_PREEMPT_RESV): RS reservation slots per node, NUMA as above (pl unused without)
+template <bool NUMA, int RS>
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_r(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                               const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                               const DevPre *__restrict__ pre, int32_t n_pre,
+                                                               int32_t *__restrict__ count,
+                                                               PreemptPartial *__restrict__ part,
+                                                               koordhip_preempt_node *__restrict__ per_node,
+                                                               NumaPlane pl) {
+  preempt_tiles<false, NUMA, RS>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
 }
 
 // Phase 1 of the sequential dry run: one tile of preemptors on the loaded
@@ -585,13 +668,13 @@ __global__ __launch_bounds__(64) void k_preempt_pick(const PreemptPartial *__res
 
 // one thread per preemptor: its chosen node again, writing the victims (vout is -1 filled by the caller).
 // NUMA: a chosen node is a CANDIDATE, so its frozen verdict is "passes" and only filterAmplifiedCPUs is left.
-template <bool NUMA>
+template <bool NUMA, int RS = 0>
 __device__ __forceinline__ void preempt_victims(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
                                                 const int32_t *__restrict__ off, const PdbAllowed &pdb,
                                                 const DevPre *__restrict__ pre, int32_t n_pre,
                                                 const koordhip_preempt_result *__restrict__ res,
                                                 int32_t *__restrict__ vout, int32_t vmax) {
-  const DevCfg c = envelope<NUMA>(cfg);
+  const DevCfg c = envelope<NUMA, RS>(cfg);
   const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
   if (p >= n_pre) return;
   const int32_t i = res[p].node;
@@ -599,13 +682,13 @@ __device__ __forceinline__ void preempt_victims(const DevCfg &cfg, const DevNode
   NV v{};
   const Need all = need_all(c);
   load_node(v, d, i, all, c);
-  NumaRowRS<1> nr{};
-  load_walk_numa<NUMA>(nr, c, d, i, all);
+  WalkRow<RS> nr{};
+  load_walk_numa<NUMA, RS>(nr, c, d, i, all);
   const int32_t lo = off[i];
   const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
   const DevPre P = pre[p];
-  (void)preempt_node<EMIT_IDX, false, NUMA>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
-                                            NodeOverlay{}, 0u);
+  (void)preempt_node<EMIT_IDX, false, NUMA, RS>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
+                                                NodeOverlay{}, 0u);
 }
 
 __global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
@@ -622,6 +705,15 @@ __global__ __launch_bounds__(64) void k_preempt_victims_n(DevCfg cfg, DevNodes d
                                                           const koordhip_preempt_result *__restrict__ res,
                                                           int32_t *__restrict__ vout, int32_t vmax) {
   preempt_victims<true>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
+}
+
+template <bool NUMA, int RS>
+__global__ __launch_bounds__(64) void k_preempt_victims_r(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                          const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                          const DevPre *__restrict__ pre, int32_t n_pre,
+                                                          const koordhip_preempt_result *__restrict__ res,
+                                                          int32_t *__restrict__ vout, int32_t vmax) {
+  preempt_victims<NUMA, RS>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
 }
 
 // ---------------------------------------------------------------------------
@@ -882,9 +974,13 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
 
 size_t preempt_plane_words(int32_t n, int32_t n_pre) { return (size_t)std::max(n_pre, 0) * 2 * (((size_t)n + 63) / 64); }
 
-// NodeNUMAResource in the Filter needs the plane, Reservation is outside the envelope
-static bool preempt_profile_ok(const DevCfg &c, const uint64_t *plane) {
-  if (c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION)) return false;
+int preempt_resv_slots(const DevCfg &c) { return c.resv_slots > 1 ? KOORDHIP_RESV_SLOTS : 1; }
+
+// NodeNUMAResource in the Filter needs the plane, Reservation state the walk with rs slots (0: none; 1 or
+// KOORDHIP_RESV_SLOTS as the snapshot's resv_slots ask)
+static bool preempt_profile_ok(const DevCfg &c, const uint64_t *plane, int rs = 0) {
+  const bool resv = c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION);
+  if (resv ? rs != preempt_resv_slots(c) : rs != 0) return false;
   return ((c.filt & KOORDHIP_PLUGIN_NUMA) != 0) == (plane != nullptr);
 }
 
@@ -900,13 +996,24 @@ hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre 
 
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, hipStream_t s) {
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, int rs,
+                          hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (!preempt_profile_ok(c, plane)) return hipErrorInvalidValue;
+  if (!preempt_profile_ok(c, plane, rs)) return hipErrorInvalidValue;
   if (per_node && n_pre != 1) return hipErrorInvalidValue;
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
-  if (plane)
+  if (rs) {
+    const NumaPlane pl{plane, (d.n + 63) / 64};
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part,
+                         per_node, pl);
+    };
+    if (rs > 1)
+      plane ? go(k_preempt_r<true, KOORDHIP_RESV_SLOTS>) : go(k_preempt_r<false, KOORDHIP_RESV_SLOTS>);
+    else
+      plane ? go(k_preempt_r<true, 1>) : go(k_preempt_r<false, 1>);
+  } else if (plane)
     hipLaunchKernelGGL(k_preempt_n, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part,
                        per_node, NumaPlane{plane, (d.n + 63) / 64});
   else
@@ -954,11 +1061,21 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, hipStream_t s) {
+                               int32_t max_victims, int rs, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
   if (victims && max_victims > 0) {
-    if (c.filt & KOORDHIP_PLUGIN_NUMA)
+    if (rs) {
+      const bool numa = (c.filt & KOORDHIP_PLUGIN_NUMA) != 0;
+      auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims,
+                           max_victims);
+      };
+      if (rs > 1)
+        numa ? go(k_preempt_victims_r<true, KOORDHIP_RESV_SLOTS>) : go(k_preempt_victims_r<false, KOORDHIP_RESV_SLOTS>);
+      else
+        numa ? go(k_preempt_victims_r<true, 1>) : go(k_preempt_victims_r<false, 1>);
+    } else if (c.filt & KOORDHIP_PLUGIN_NUMA)
       hipLaunchKernelGGL(k_preempt_victims_n, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre,
                          res, victims, max_victims);
     else

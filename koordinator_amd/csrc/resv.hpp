@@ -289,6 +289,155 @@ __device__ __forceinline__ bool resv_filter(const DevPod &p, const NV &v, const 
   return pass || nar == 0;
 }
 
+// ---- the preemption dry run's cycle state (preempt.hip, KOORDHIP_PREEMPT_RESV)
+// What the plugin's PreFilterExtensions keep per (preemptor, node) while
+// SelectVictimsOnNode removes and re-adds pods (plugin.go:254-323), over the
+// five row resources: pn = state.preemptible[node], pr[q] =
+// state.preemptibleInRRs[node][slot q's UID].  An entry is present iff some
+// resource is non-zero.  pq / touched: nodeRState.podRequested cpu / memory,
+// the clone taken before the matched restore (transformer.go:129), frozen for
+// the call; a node without a class 1 / 2 slot has no nodeRState (all zero).
+template <int S>
+struct ResvPre {
+  double pn[KOORDHIP_NRES];
+  double pr[S][KOORDHIP_NRES];
+  double pq[2];
+  bool touched;
+};
+
+__device__ __forceinline__ bool resv_present(const double *x) {
+  bool on = false;
+#pragma unroll
+  for (int k = 0; k < KOORDHIP_NRES; k++) on |= x[k] != 0.0;
+  return on;
+}
+
+// w0: the row after resv_restore for p (mm: its matched slots)
+template <int S>
+__device__ __forceinline__ void resv_pre_init(ResvPre<S> &s, const NV &w0, const NumaRowRS<S> &r, const DevPod &p,
+                                              uint32_t mm) {
+  s.touched = false;
+  s.pq[0] = w0.r[KOORDHIP_RES_CPU];
+  s.pq[1] = w0.r[KOORDHIP_RES_MEM];
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    s.touched |= resv_class(r.rs[q], p) != 0;
+    if ((mm >> q) & 1u) {
+      s.pq[0] += r.rs[q].ra[0];
+      s.pq[1] += r.rs[q].ra[1];
+    }
+#pragma unroll
+    for (int k = 0; k < KOORDHIP_NRES; k++) s.pr[q][k] = 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < KOORDHIP_NRES; k++) s.pn[k] = 0.0;
+  if (!s.touched) s.pq[0] = s.pq[1] = 0.0;
+}
+
+// RemovePod (sign < 0) / AddPod (sign > 0) of a listed pod bound to slot
+// `slot` (-1: to none).  A pod without requests moves nothing (:259, :298).
+// AddPod of a bound pod is restated literally (:278-286): the entry is deleted
+// when the difference is zero in every resource and otherwise KEEPS ITS OLD
+// VALUE -- the reference never stores the difference.
+template <int S>
+__device__ __forceinline__ void resv_pre_move(ResvPre<S> &s, const DevPod &a, int slot, int sign) {
+  if (!resv_present(a.req)) return;
+  if (slot < 0) {
+#pragma unroll
+    for (int k = 0; k < KOORDHIP_NRES; k++)
+      s.pn[k] = sign < 0 ? s.pn[k] + a.req[k] : (s.pn[k] > a.req[k] ? s.pn[k] - a.req[k] : 0.0);
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    if (q != slot) continue;
+    if (sign < 0) {
+#pragma unroll
+      for (int k = 0; k < KOORDHIP_NRES; k++) s.pr[q][k] += a.req[k];
+    } else {
+      bool zero = true;
+#pragma unroll
+      for (int k = 0; k < KOORDHIP_NRES; k++) zero &= !(s.pr[q][k] > a.req[k]);
+      if (zero)
+#pragma unroll
+        for (int k = 0; k < KOORDHIP_NRES; k++) s.pr[q][k] = 0.0;
+    }
+  }
+}
+
+// fitsNode (plugin.go:445-494) on the walk's row w: the pod count of the moved
+// NodeInfo, the frozen podRequested (s.pq; v0: the loaded row, whose ephemeral
+// storage and batch amounts the restore leaves alone), rRemained of the
+// reservation (rem; 0 without one), the matched Allocated and `pre`.
+template <int S>
+__device__ __forceinline__ bool resv_fits_node(const DevPod &p, const NV &w, const NV &v0, const ResvPre<S> &s,
+                                               int nmatch, const double *rem, const double *rall, const double *pre) {
+  bool fits = !(w.npods - nmatch + 1 > w.a_pods);
+  if (p.flags & KOORDHIP_POD_HAS_REQ) {
+#pragma unroll
+    for (int k = 0; k < 2; k++) fits &= !(p.req[k] > w.a[k] - (s.pq[k] - rem[k] - rall[k] - pre[k]));
+    auto rest = [&](int k) { return !(p.req[k] > w.a[k] - ((s.touched ? v0.r[k] : 0.0) - pre[k])); };
+    fits &= rest(KOORDHIP_RES_EPH);
+    if (p.flags & KOORDHIP_POD_REQ_BCPU) fits &= rest(KOORDHIP_RES_BCPU);
+    if (p.flags & KOORDHIP_POD_REQ_BMEM) fits &= rest(KOORDHIP_RES_BMEM);
+  }
+  return fits;
+}
+
+// filterWithReservations (plugin.go:373-440) with the preemptible state s.
+// With nothing present it is resv_filter (nmatch > 0) / the affinity test.
+template <int S>
+__device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
+                                                uint32_t mm, int nmatch, const ResvPre<S> &s) {
+  const bool pn_on = resv_present(s.pn);
+  const double none[2] = {0.0, 0.0};
+  if (nmatch == 0) {
+    if (p.flags & KOORDHIP_POD_RESV_AFFINITY) return false;
+    bool any = pn_on;
+#pragma unroll
+    for (int q = 0; q < S; q++) any |= resv_present(s.pr[q]);
+    return !any || resv_fits_node(p, w, v0, s, 0, none, none, s.pn);  // a failure: ErrReasonPreemptionFailed
+  }
+  double rall[2] = {0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < S; q++)
+    if ((mm >> q) & 1u) {
+      rall[0] += r.rs[q].rd[0];
+      rall[1] += r.rs[q].rd[1];
+    }
+  bool pass = false;
+  int tot[3] = {0, 0, 0}, bad[3] = {0, 0, 0};  // Default, Aligned, Restricted
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    if (!((mm >> q) & 1u)) continue;
+    const ResvSlot &x = r.rs[q];
+    const uint32_t pol = KOORDHIP_RESV_POLICY(x.rf);
+    const bool pr_on = resv_present(s.pr[q]);
+    double pre[KOORDHIP_NRES];
+#pragma unroll
+    for (int k = 0; k < KOORDHIP_NRES; k++) pre[k] = s.pr[q][k] + s.pn[k];
+    const double rem[2] = {rem_of(x, 0), rem_of(x, 1)};  // from the unmodified Allocated
+    const bool fits = resv_fits_node(p, w, v0, s, nmatch, rem, rall, pre);
+    bool ok = fits;
+    if (pol == 0) {
+      ok = !(pr_on || pn_on) || fits;
+    } else if (pol == 2) {  // LessThanOrEqual(podRequests, Allocatable - (Allocated - preemptibleInRR))
+#pragma unroll
+      for (int k = 0; k < 2; k++) {
+        const double held = pr_on ? (x.rd[k] > s.pr[q][k] ? x.rd[k] - s.pr[q][k] : 0.0) : x.rd[k];
+        const double left = x.ra[k] > held ? x.ra[k] - held : 0.0;
+        ok &= !(rkey(x.rf, k) && pkey(p, k) && p.req[k] > left);
+      }
+    }
+    const int g = pol == 0 ? 0 : (pol == 1 ? 1 : 2);
+    tot[g]++;
+    bad[g] += ok ? 0 : 1;
+    pass |= ok && pol != 0;
+  }
+  if (pass) return true;
+  return !((tot[0] > 0 && tot[0] == bad[0]) || (tot[1] > 0 && tot[1] == bad[1]) || (tot[2] > 0 && tot[2] == bad[2]));
+}
+
 // FilterReservation of a matched reservation: a nomination candidate
 __device__ __forceinline__ bool resv_candidate(const DevPod &p, const ResvSlot &r, bool xh = false, uint32_t xf = 0u) {
   bool inter = xh && (xf & RX_INTER), nonzero = xh && (xf & RX_NZ);

@@ -366,16 +366,23 @@ class PlacementEngine:
         abi.check(self.lib, self.lib.koordhip_preempt_load_pods(self._ctx, a.ctypes.data, len(a),
                                                                 abi.ptr(pdb, C.c_int32), len(pdb)))
 
-    def preempt_set_mode(self, numa_frozen: bool = False, flags: int = None):
+    def preempt_set_mode(self, numa_frozen: bool = False, resv: bool = False, flags: int = None):
         """numa_frozen: the dry-run calls accept NodeNUMAResource in the Filter,
         with the plugin's verdict frozen for the call: victims' cpusets and
         zone amounts are not freed and a nominated cpuset preemptor holds no
-        CPUs, as in the reference (include/koordhip.h).  The mode is the
-        context's; False restores the refusal.  flags: the raw
+        CPUs, as in the reference (include/koordhip.h).  resv: preempt() and
+        preempt_node_verdicts() accept Reservation state: the walk starts from
+        the restored row and keeps the plugin's AddPod / RemovePod state
+        (listed pods name their reservation slot, preemption.assigned_records);
+        preempt_stream() still refuses it.  The shipped profile needs both;
+        on a profile with NodeNUMAResource in the Filter and without the
+        Reservation plugin resv=True is refused (KOORDHIP_EINVAL).
+        The mode is the context's; False restores the refusal.  flags: the raw
         abi.PREEMPT_* word instead."""
         if not hasattr(self.lib, "koordhip_preempt_set_mode"):
             raise RuntimeError("this libkoordhip build has no koordhip_preempt_set_mode")
-        word = (abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) if flags is None else int(flags)
+        word = ((abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) | (abi.PREEMPT_RESV if resv else 0)) if flags is None \
+            else int(flags)
         abi.check(self.lib, self.lib.koordhip_preempt_set_mode(self._ctx, word))
 
     def preempt(self, preemptors: np.ndarray, max_victims: int = 0):

@@ -7,6 +7,11 @@ pods that sit on the nodes, the preemptor records and a view of the result.
     preemptor_records  pending pods + their quotas' postFilterState -> abi.PREEMPTOR_DTYPE
     PreemptionResult   node name + victim pod keys of one preemptor
 
+With Reservation state (PlacementEngine.preempt_set_mode(resv=True)) pass
+assigned_records the per-node slot order of the snapshot's reservation columns
+(`reservation_slots`): a listed pod names the slot of the reservation it was
+assumed into, and reserve pods are not listed.
+
 PodEligibleToPreemptOthers and nominated pods stay with the caller.
 
 For a batch answered by PlacementEngine.preempt_stream (koordhip_preempt_stream)
@@ -27,6 +32,7 @@ import numpy as np
 from . import abi, k8s
 from .config import Profile
 from .marshal import MarshalError, pod_record
+from .reservation import Reservation, is_reserve_pod, reservation_allocated
 from .topologyspread import LabelSelector
 
 LABEL_QUOTA_NAME = "quota.scheduling.koordinator.sh/name"           # apis/extension/elastic_quota.go:37
@@ -97,16 +103,26 @@ class QuotaIds:
 def assigned_records(pods: Iterable[k8s.Pod], profile: Profile, node_index: Dict[str, int], quotas: QuotaIds,
                      pdbs: Sequence[PodDisruptionBudget] = (), now_ns: int = 0,
                      start_time_ns: Optional[Dict[str, int]] = None, in_quota: Optional[Callable[[k8s.Pod], bool]] = None,
-                     quota_of: Callable[[k8s.Pod], str] = quota_name, resources=QUOTA_RESOURCES, static_classes=None):
+                     quota_of: Callable[[k8s.Pod], str] = quota_name, resources=QUOTA_RESOURCES, static_classes=None,
+                     reservation_slots: Optional[Dict[int, List[Reservation]]] = None):
     """(abi.ASSIGNED_DTYPE records, DisruptionsAllowed per PDB, pod keys) of the
     pods bound to the snapshot's nodes (pod.node_name in `node_index`).
     `start_time_ns`: status.startTime by pod key (absent: `now_ns`, as
-    GetPodStartTime).  `in_quota(pod)`: quotaInfo.IsPodExist (default: every pod)."""
+    GetPodStartTime).  `in_quota(pod)`: quotaInfo.IsPodExist (default: every pod).
+    `reservation_slots`: node row -> its reservations in slot order, as
+    reservation.available_by_node returned them for reservation_columns (the
+    KOORDHIP_PREEMPT_RESV mode).  With it a pod's reservation-allocated
+    annotation becomes abi.asg_resv_slot(slot) in its flags (matched by UID;
+    MarshalError when its node holds no such reservation)
+    and reserve pods are skipped: the plugin's AddPod / RemovePod skip them and
+    the dry run never lists them as victims."""
     if len(pdbs) > abi.PREEMPT_PDBS:
         raise MarshalError(f"{len(pdbs)} PodDisruptionBudgets: the table takes {abi.PREEMPT_PDBS}")
     if len(resources) > abi.PREEMPT_QRES:
         raise MarshalError(f"{len(resources)} quota dimensions: the records take {abi.PREEMPT_QRES}")
     pods = [p for p in pods if p.node_name in node_index]
+    if reservation_slots is not None:
+        pods = [p for p in pods if not is_reserve_pod(p)]
     out = np.zeros(len(pods), abi.ASSIGNED_DTYPE)
     for j, pod in enumerate(pods):
         rec = out[j]
@@ -120,6 +136,14 @@ def assigned_records(pods: Iterable[k8s.Pod], profile: Profile, node_index: Dict
         rec["pdb_mask"] = sum(1 << i for i, pdb in enumerate(pdbs) if pdb_matches(pdb, pod))
         reqs, _ = k8s.pod_requests_and_limits(pod)
         rec["qreq"] = _quantities(reqs, resources)
+        bound = reservation_allocated(pod) if reservation_slots is not None else None
+        if bound is not None and bound[0]:             # (an empty UID counts as not bound, plugin.go:270,309)
+            slots = reservation_slots.get(int(rec["node"]), [])
+            q = next((k for k, r in enumerate(slots) if r.uid == bound[0]), None)
+            if q is None:
+                raise MarshalError(f"pod {pod.key}: bound to reservation {bound[1]!r} (uid {bound[0]}), which has no "
+                                   f"slot on node {pod.node_name}")
+            rec["flags"] = int(rec["flags"]) | abi.asg_resv_slot(q)
     return out, np.array([p.disruptions_allowed for p in pdbs], np.int32), [p.key for p in pods]
 
 
