@@ -3700,34 +3700,62 @@ int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
   return 0;
 }
 
-// NodeNUMAResource is in the Filter and the host accepted the frozen verdict
-static bool preempt_numa_mode(const koordhip_ctx *c) {
-  return (c->pre_mode & KOORDHIP_PREEMPT_NUMA_FROZEN) && (c->dc.filt & KOORDHIP_PLUGIN_NUMA);
-}
-
-// The context has Reservation state (the Filter plugin or reservation columns) ...
-static bool preempt_resv_state(const koordhip_ctx *c) {
-  return c->dc.resv || (c->dc.filt & KOORDHIP_PLUGIN_RESERVATION);
-}
-// ... and the host accepted the walk that keeps the plugin's AddPod / RemovePod state: its slots per row, else 0
-static int preempt_resv_rs(const koordhip_ctx *c) {
-  return (c->pre_mode & KOORDHIP_PREEMPT_RESV) && preempt_resv_state(c) ? kh::preempt_resv_slots(c->dc) : 0;
-}
-
-// The NUMA mode's pre-pass for the uploaded preemptors; *plane stays NULL outside the mode.
-static int preempt_plane(koordhip_ctx *c, int32_t n_pre, const uint64_t **plane) {
-  *plane = nullptr;
-  if (!preempt_numa_mode(c) || n_pre <= 0 || c->n <= 0) return 0;
+// The read-only inputs of one dry-run call, typed: the node-sorted table, the uploaded preemptors, the call's
+// walk and its verdict plane.  preempt_inputs runs the NUMA mode's pre-pass for the uploaded preemptors; plane
+// stays NULL outside the mode.
+struct PreemptInputs {
+  const kh::DevAsg *tab;
+  const int32_t *off;
+  const kh::DevPre *dp;
+  const uint64_t *plane;
+  kh::WalkMode mode;
+};
+static int preempt_inputs(koordhip_ctx *c, int32_t n_pre, PreemptInputs *in) {
+  in->tab = static_cast<const kh::DevAsg *>(c->d_pre_tab);
+  in->off = kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), c->n);
+  in->dp = static_cast<const kh::DevPre *>(c->d_pre_in);
+  in->mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
+  in->plane = nullptr;
+  if (!in->mode.numa || n_pre <= 0 || c->n <= 0) return 0;
   if (int e = ensure(c, &c->d_pre_plane, &c->pre_plane_cap, kh::preempt_plane_words(c->n, n_pre) * sizeof(uint64_t)))
     return e;
-  uint64_t *w = static_cast<uint64_t *>(c->d_pre_plane);
-  HIP_TRY(kh::launch_preempt_numa(c->dc, c->d, static_cast<const kh::DevPre *>(c->d_pre_in), n_pre, w, c->stream));
-  *plane = w;
+  HIP_TRY(kh::launch_preempt_numa(c->dc, c->d, in->dp, n_pre, static_cast<uint64_t *>(c->d_pre_plane), c->stream));
+  in->plane = static_cast<const uint64_t *>(c->d_pre_plane);
   return 0;
 }
 
-// The checks the dry-run calls share, and the preemptors' upload (stream: koordhip_preempt_stream asks).
-static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, bool stream = false) {
+// A call's buffers carved in order from one allocation, every size rounded up to `align` bytes.  preempt_carve
+// runs the caller's layout twice: to measure (base NULL: `at` ends as the size to ensure()), then on the buffer.
+extern "C++" {
+struct Carve {
+  size_t align;
+  char *base;
+  size_t at = 0;
+  template <class T>
+  T *take(size_t count) {
+    char *p = base ? base + at : nullptr;
+    at += (count * sizeof(T) + align - 1) & ~(align - 1);
+    return reinterpret_cast<T *>(p);
+  }
+};
+template <class F>
+static int preempt_carve(koordhip_ctx *c, void **buf, size_t *cap, size_t align, F layout) {
+  Carve measure{align, nullptr}, cv{align, nullptr};
+  layout(measure);
+  if (int e = ensure(c, buf, cap, measure.at)) return e;
+  cv.base = static_cast<char *>(*buf);
+  layout(cv);
+  return 0;
+}
+}  // extern "C++"
+
+// The checks the dry-run calls share, and the preemptors' upload (out: where the call's answer goes; stream:
+// koordhip_preempt_stream asks).
+static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, const void *out,
+                         int32_t max_victims, bool stream) {
+  if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
+  if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
+  const kh::WalkMode mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (!c->pre_loaded)
     return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
@@ -3735,19 +3763,19 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (c->seq || c->seq_profile)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: the profile / snapshot evaluates in the sequential cycle "
                                  "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
-  if ((c->dc.filt & KOORDHIP_PLUGIN_NUMA) && !preempt_numa_mode(c))
+  if ((c->dc.filt & KOORDHIP_PLUGIN_NUMA) && !mode.numa)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with NodeNUMAResource in the Filter (it has no "
                                  "PreFilterExtensions: its state does not move in a dry run) unless "
                                  "koordhip_preempt_set_mode(KOORDHIP_PREEMPT_NUMA_FROZEN) accepted that");
-  if (preempt_resv_state(c)) {
+  if (mode.resv) {
     if (stream)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not with Reservation plugin state, with or without "
                                    "KOORDHIP_PREEMPT_RESV (earlier preemptors' victims would have to leave the "
                                    "reservations' Allocated and assigned counts)");
-    if (!preempt_resv_rs(c))
+    if (!mode.rs)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
                                    "not kept) unless koordhip_preempt_set_mode(KOORDHIP_PREEMPT_RESV) asked for it");
-    if (preempt_numa_mode(c) && c->dc.resv_cpus)
+    if (mode.numa && c->dc.resv_cpus)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_NUMA_FROZEN with KOORDHIP_PREEMPT_RESV not on a "
                                    "snapshot whose reservations hold CPUs (resv_cpus: the frozen NUMA verdict does not "
                                    "model their restore)");
@@ -3758,7 +3786,7 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
     pods[p] = pre[p].pod;
     if (pods[p].flags & (KOORDHIP_POD_RESERVE | KOORDHIP_POD_RESV_OPERATING))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: reserve / reservation-operating-mode pods are not covered");
-    if (preempt_numa_mode(c) && (pods[p].flags & KOORDHIP_POD_NUMA_ERROR))
+    if (mode.numa && (pods[p].flags & KOORDHIP_POD_NUMA_ERROR))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: a preemptor with KOORDHIP_POD_NUMA_ERROR (a PreFilter error "
                                    "aborts the cycle: there is no PostFilter)");
     if (pre[p].quota < -1) return fail(KOORDHIP_EINVAL, "koordhip_preempt: quota is an id >= 0, or -1 (skip)");
@@ -3791,42 +3819,43 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   return 0;
 }
 
+// The entry of koordhip_preempt and koordhip_preempt_stream: preempt_ready, then the answer that needs no
+// launch.  With no preemptor or no node the caller returns; without a node nobody has a pick or a victim.
+static int preempt_enter(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                         int32_t *victims, int32_t max_victims, bool stream) {
+  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream)) return e;
+  if (n_pre == 0 || c->n > 0) return 0;
+  std::memset(out, 0, (size_t)n_pre * sizeof(*out));
+  for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
+  if (victims) std::fill_n(victims, (size_t)n_pre * max_victims, -1);
+  return 0;
+}
+
 int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
                      int32_t *victims, int32_t max_victims) {
-  if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
-  if (int e = preempt_ready(c, pre, n_pre)) return e;
-  if (n_pre == 0) return 0;
-  const int32_t n = c->n;
+  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, false)) return e;
+  if (n_pre == 0 || c->n == 0) return 0;
+  const size_t nb = (size_t)kh::preempt_blocks(c->n);
   const size_t nv = victims ? (size_t)n_pre * max_victims : 0;
-  if (n == 0) {
-    std::memset(out, 0, (size_t)n_pre * sizeof(*out));
-    for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
-    for (size_t k = 0; k < nv; k++) victims[k] = -1;
-    return 0;
-  }
-  const size_t nb = (size_t)kh::preempt_blocks(n);
-  const size_t cb = ((size_t)n_pre * KOORDHIP_PREEMPT_STATUSES * sizeof(int32_t) + 7) & ~(size_t)7;
-  const size_t pb = (size_t)n_pre * nb * sizeof(kh::PreemptPartial);
-  const size_t rb = (size_t)n_pre * sizeof(koordhip_preempt_result);
-  const size_t vb = nv * sizeof(int32_t);
-  if (int e = ensure(c, &c->d_pre_out, &c->pre_out_cap, cb + pb + rb + vb)) return e;
-  char *base = static_cast<char *>(c->d_pre_out);
-  int32_t *d_cnt = reinterpret_cast<int32_t *>(base);
-  kh::PreemptPartial *d_part = reinterpret_cast<kh::PreemptPartial *>(base + cb);
-  koordhip_preempt_result *d_res = reinterpret_cast<koordhip_preempt_result *>(base + cb + pb);
-  int32_t *d_vic = nv ? reinterpret_cast<int32_t *>(base + cb + pb + rb) : nullptr;
-  const kh::DevAsg *tab = static_cast<const kh::DevAsg *>(c->d_pre_tab);
-  const int32_t *off = kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n);
-  const kh::DevPre *dp = static_cast<const kh::DevPre *>(c->d_pre_in);
-  const uint64_t *plane = nullptr;
-  if (int e = preempt_plane(c, n_pre, &plane)) return e;
-  HIP_TRY(hipMemsetAsync(d_cnt, 0, cb, c->stream));
+  const size_t rb = (size_t)n_pre * sizeof(koordhip_preempt_result), vb = nv * sizeof(int32_t);
+  int32_t *d_cnt, *d_vic;
+  kh::PreemptPartial *d_part;
+  koordhip_preempt_result *d_res;
+  if (int e = preempt_carve(c, &c->d_pre_out, &c->pre_out_cap, 8, [&](Carve &cv) {
+        d_cnt = cv.take<int32_t>((size_t)n_pre * KOORDHIP_PREEMPT_STATUSES);
+        d_part = cv.take<kh::PreemptPartial>((size_t)n_pre * nb);
+        d_res = cv.take<koordhip_preempt_result>(n_pre);
+        d_vic = nv ? cv.take<int32_t>(nv) : nullptr;
+      }))
+    return e;
+  PreemptInputs in;
+  if (int e = preempt_inputs(c, n_pre, &in)) return e;
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, (char *)d_part - (char *)d_cnt, c->stream));  // the counts, rounded up
   if (nv) HIP_TRY(hipMemsetAsync(d_vic, 0xFF, vb, c->stream));
-  const int rs = preempt_resv_rs(c);
-  HIP_TRY(kh::launch_preempt(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, nullptr, plane, rs, c->stream));
-  HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, tab, off, c->pre_pdb, dp, n_pre, d_cnt, d_part, d_res, d_vic, max_victims,
-                                  rs, c->stream));
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, d_cnt, d_part, nullptr, in.plane,
+                             in.mode, c->stream));
+  HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, d_cnt, d_part, d_res, d_vic,
+                                  max_victims, in.mode, c->stream));
   HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, d_vic, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -3838,73 +3867,45 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
 int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
                             int32_t *victims, int32_t max_victims, koordhip_preempt_stream_stats *stats) {
   static_assert(sizeof(koordhip_preempt_stream_stats) == 24, "stream stats");
-  if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
-  if (int e = preempt_ready(c, pre, n_pre, true)) return e;
+  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, true)) return e;
   if (stats) *stats = koordhip_preempt_stream_stats{};
-  if (n_pre == 0) return 0;
+  if (n_pre == 0 || c->n == 0) return 0;
   const int32_t n = c->n;
   const size_t nv = victims ? (size_t)n_pre * max_victims : 0;
-  if (n == 0) {
-    std::memset(out, 0, (size_t)n_pre * sizeof(*out));
-    for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
-    for (size_t k = 0; k < nv; k++) victims[k] = -1;
-    return 0;
-  }
   const size_t nb = (size_t)kh::preempt_blocks(n);
-  size_t at = 0;
-  auto take = [&at](size_t bytes) {
-    const size_t o = at;
-    at += (bytes + 15) & ~(size_t)15;
-    return o;
-  };
-  // cleared to 0 before the first launch: gone .. stats
-  const size_t o_gone = take((size_t)n * 2 * sizeof(uint64_t));
-  const size_t o_freed = take((size_t)n_pre * KOORDHIP_PREEMPT_QRES * sizeof(int64_t));
-  const size_t o_touched = take(nb * sizeof(int32_t));
-  const size_t o_qflag = take((size_t)n_pre * sizeof(int32_t));
-  const size_t o_stats = take(sizeof(koordhip_preempt_stream_stats));
-  const size_t zero_bytes = at;
-  // set to -1: head, victims
-  const size_t o_head = take((size_t)n * sizeof(int32_t));
-  const size_t o_vic = take(nv * sizeof(int32_t));
-  const size_t ff_bytes = at - o_head;
-  // written before they are read
-  const size_t o_part = take((size_t)n_pre * nb * sizeof(kh::PreemptPartial));
-  const size_t o_bcnt = take((size_t)n_pre * nb * KOORDHIP_PREEMPT_STATUSES * sizeof(int32_t));
-  const size_t o_res = take((size_t)n_pre * sizeof(koordhip_preempt_result));
-  const size_t o_nom = take((size_t)n_pre * sizeof(kh::NomEntry));
-  const size_t o_pdb = take(sizeof(kh::PdbAllowed));
-  const size_t o_flags = take(sizeof(kh::StreamFlags));
-  const size_t o_vpos = take(KOORDHIP_PREEMPT_NODE_PODS * sizeof(int32_t));
-  if (int e = ensure(c, &c->d_pre_st, &c->pre_st_cap, at)) return e;
-  char *base = static_cast<char *>(c->d_pre_st);
   kh::StreamState st{};
-  st.gone = reinterpret_cast<uint64_t *>(base + o_gone);
-  st.freed = reinterpret_cast<int64_t *>(base + o_freed);
-  st.touched = reinterpret_cast<int32_t *>(base + o_touched);
-  st.qflag = reinterpret_cast<int32_t *>(base + o_qflag);
-  st.stats = reinterpret_cast<koordhip_preempt_stream_stats *>(base + o_stats);
-  st.head = reinterpret_cast<int32_t *>(base + o_head);
-  st.victims = nv ? reinterpret_cast<int32_t *>(base + o_vic) : nullptr;
-  st.part = reinterpret_cast<kh::PreemptPartial *>(base + o_part);
-  st.bcnt = reinterpret_cast<int32_t *>(base + o_bcnt);
-  st.res = reinterpret_cast<koordhip_preempt_result *>(base + o_res);
-  st.nom = reinterpret_cast<kh::NomEntry *>(base + o_nom);
-  st.pdb = reinterpret_cast<kh::PdbAllowed *>(base + o_pdb);
-  st.flags = reinterpret_cast<kh::StreamFlags *>(base + o_flags);
-  st.vpos = reinterpret_cast<int32_t *>(base + o_vpos);
+  size_t zero_bytes = 0, ff_bytes = 0;
+  auto layout = [&](Carve &cv) {
+    // cleared to 0 before the first launch: gone .. stats
+    st.gone = cv.take<uint64_t>((size_t)n * 2);
+    st.freed = cv.take<int64_t>((size_t)n_pre * KOORDHIP_PREEMPT_QRES);
+    st.touched = cv.take<int32_t>(nb);
+    st.qflag = cv.take<int32_t>(n_pre);
+    st.stats = cv.take<koordhip_preempt_stream_stats>(1);
+    zero_bytes = cv.at;
+    // set to -1: head, victims
+    st.head = cv.take<int32_t>(n);
+    st.victims = nv ? cv.take<int32_t>(nv) : nullptr;
+    ff_bytes = cv.at - zero_bytes;
+    // written before they are read
+    st.part = cv.take<kh::PreemptPartial>((size_t)n_pre * nb);
+    st.bcnt = cv.take<int32_t>((size_t)n_pre * nb * KOORDHIP_PREEMPT_STATUSES);
+    st.res = cv.take<koordhip_preempt_result>(n_pre);
+    st.nom = cv.take<kh::NomEntry>(n_pre);
+    st.pdb = cv.take<kh::PdbAllowed>(1);
+    st.flags = cv.take<kh::StreamFlags>(1);
+    st.vpos = cv.take<int32_t>(KOORDHIP_PREEMPT_NODE_PODS);
+  };
+  if (int e = preempt_carve(c, &c->d_pre_st, &c->pre_st_cap, 16, layout)) return e;
   // A/B knob, read at every call: every block evaluates every preemptor again (the plain per-preemptor chain)
   const char *fe = std::getenv("KOORDHIP_PREEMPT_STREAM_FULL");
   const bool full = fe && *fe && std::strcmp(fe, "0") != 0;
-  const uint64_t *plane = nullptr;  // the verdicts of all preemptors, once, before the first
-  if (int e = preempt_plane(c, n_pre, &plane)) return e;
-  HIP_TRY(hipMemsetAsync(base, 0, zero_bytes, c->stream));
-  HIP_TRY(hipMemsetAsync(base + o_head, 0xFF, ff_bytes, c->stream));
-  HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
-                                    kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
-                                    static_cast<const kh::DevPre *>(c->d_pre_in), n_pre, st, max_victims, full,
-                                    plane, c->stream));
+  PreemptInputs in;  // the plane: the verdicts of all preemptors, once, before the first
+  if (int e = preempt_inputs(c, n_pre, &in)) return e;
+  HIP_TRY(hipMemsetAsync(st.gone, 0, zero_bytes, c->stream));
+  HIP_TRY(hipMemsetAsync(st.head, 0xFF, ff_bytes, c->stream));
+  HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, st, max_victims, full,
+                                    in.plane, in.mode, c->stream));
   HIP_TRY(hipMemcpyAsync(out, st.res, (size_t)n_pre * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, st.victims, nv * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, sizeof(*stats), hipMemcpyDeviceToHost, c->stream));
@@ -3913,26 +3914,24 @@ int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int3
 }
 
 int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pre, koordhip_preempt_node *per_node) {
-  if (!c || !pre || !per_node) return fail(KOORDHIP_EINVAL, "NULL argument");
-  if (int e = preempt_ready(c, pre, 1)) return e;
+  if (int e = preempt_ready(c, pre, 1, per_node, 0, false)) return e;
   const int32_t n = c->n;
   if (n == 0) return 0;
-  const size_t nb = (size_t)kh::preempt_blocks(n);
-  const size_t cb = 8 * sizeof(int32_t);
-  const size_t pb = nb * sizeof(kh::PreemptPartial);
-  const size_t vb = (size_t)n * sizeof(koordhip_preempt_node);
-  if (int e = ensure(c, &c->d_pre_out, &c->pre_out_cap, cb + pb + vb)) return e;
-  char *base = static_cast<char *>(c->d_pre_out);
-  koordhip_preempt_node *d_ver = reinterpret_cast<koordhip_preempt_node *>(base + cb + pb);
-  const uint64_t *plane = nullptr;
-  if (int e = preempt_plane(c, 1, &plane)) return e;
-  HIP_TRY(hipMemsetAsync(base, 0, cb, c->stream));
-  HIP_TRY(kh::launch_preempt(c->dc, c->d, static_cast<const kh::DevAsg *>(c->d_pre_tab),
-                             kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), n), c->pre_pdb,
-                             static_cast<const kh::DevPre *>(c->d_pre_in), 1, reinterpret_cast<int32_t *>(base),
-                             reinterpret_cast<kh::PreemptPartial *>(base + cb), d_ver, plane, preempt_resv_rs(c),
+  int32_t *d_cnt;
+  kh::PreemptPartial *d_part;
+  koordhip_preempt_node *d_ver;
+  if (int e = preempt_carve(c, &c->d_pre_out, &c->pre_out_cap, 8, [&](Carve &cv) {
+        d_cnt = cv.take<int32_t>(8);
+        d_part = cv.take<kh::PreemptPartial>(kh::preempt_blocks(n));
+        d_ver = cv.take<koordhip_preempt_node>(n);
+      }))
+    return e;
+  PreemptInputs in;
+  if (int e = preempt_inputs(c, 1, &in)) return e;
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, 8 * sizeof(int32_t), c->stream));
+  HIP_TRY(kh::launch_preempt(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, 1, d_cnt, d_part, d_ver, in.plane, in.mode,
                              c->stream));
-  HIP_TRY(hipMemcpyAsync(per_node, d_ver, vb, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(per_node, d_ver, (size_t)n * sizeof(*per_node), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -51,19 +51,36 @@ size_t preempt_ws_ints(int32_t n, int32_t m);
 inline int32_t *preempt_off(int32_t *ws, int32_t n) { return ws + n + 1; }
 hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s);
 
+// Which walk a dry-run call runs: what the profile / snapshot holds and what
+// koordhip_preempt_set_mode's flags accepted of it.  The launchers pick their
+// kernels' instantiation from numa and rs alone.
+struct WalkMode {
+  bool numa;  // NodeNUMAResource is in the Filter and the host accepted the frozen verdict: the walk reads the plane
+  bool resv;  // the context has Reservation state (the Filter plugin or reservation columns) ...
+  int rs;     // ... and the host accepted the walk that keeps the plugin's AddPod / RemovePod state: the
+              // reservation slots per row (1, or KOORDHIP_RESV_SLOTS where the snapshot's resv_slots ask), else 0
+};
+inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
+  WalkMode m{};
+  m.numa = (pre_mode & KOORDHIP_PREEMPT_NUMA_FROZEN) && (c.filt & KOORDHIP_PLUGIN_NUMA);
+  m.resv = c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION);
+  m.rs = (pre_mode & KOORDHIP_PREEMPT_RESV) && m.resv ? (c.resv_slots > 1 ? KOORDHIP_RESV_SLOTS : 1) : 0;
+  return m;
+}
+
 // The dry run of pre[0, n_pre) on the current rows.  count [n_pre][5] (zeroed by
 // the caller) receives the nodes per status, part [n_pre][preempt_blocks(n)]
 // the workgroups' best candidates; per_node (n_pre = 1 only, may be NULL) every
-// node's verdict.  plane: NULL, or with NodeNUMAResource in the Filter the
-// words launch_preempt_numa wrote for these preemptors (the walk then reads the
-// plugin's verdict there and evaluates filterAmplifiedCPUs on every row).
-// rs: 0, or with Reservation state (KOORDHIP_PREEMPT_RESV) preempt_resv_slots(c):
-// the walk then starts from the restored row and keeps the plugin's AddPod /
-// RemovePod state; DevAsg::flags bits 8-11 name the slot a listed pod is bound to.
-int preempt_resv_slots(const DevCfg &c);
+// node's verdict.  m: the context's preempt_walk_mode; the call is refused
+// unless it covers every state the profile has.  plane: with m.numa the words
+// launch_preempt_numa wrote for these preemptors (the walk then reads the
+// plugin's verdict there and evaluates filterAmplifiedCPUs on every row), else
+// NULL.  With m.rs the walk starts from the restored row and keeps the plugin's
+// AddPod / RemovePod state; DevAsg::flags bits 8-11 name the slot a listed pod
+// is bound to.
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, int rs,
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, WalkMode m,
                           hipStream_t s);
 // The frozen NUMA verdict plane of pre[0, n_pre): plane [n_pre][2][ceil(n / 64)]
 // u64 (preempt_plane_words), bit b of word w is node 64 w + b; [p][0]: the
@@ -73,11 +90,11 @@ size_t preempt_plane_words(int32_t n, int32_t n_pre);
 hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
                                hipStream_t s);
 // part -> res[p].node / best (count is copied in), then the chosen nodes'
-// victims [n_pre][max_victims], -1 padded (victims may be NULL).
+// victims [n_pre][max_victims], -1 padded (victims may be NULL).  m: launch_preempt's.
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, int rs, hipStream_t s);
+                               int32_t max_victims, WalkMode m, hipStream_t s);
 
 // ---- the sequential dry run (koordhip_preempt_stream) ----------------------
 // Preemptor k is answered on the state the preemptors before it left: their
@@ -119,10 +136,11 @@ struct StreamState {
 // Phase 1 (the preemptors on the loaded state, per-block partials and counts,
 // a tile of 32 at a time) and per preemptor k: k_preempt_seq (the blocks that
 // have to evaluate k again), k_preempt_seq_pick, k_preempt_apply.  full: the
-// A/B knob, every block evaluates every preemptor again.  plane: as for
-// launch_preempt, written once before the first preemptor.  Nothing synchronises.
+// A/B knob, every block evaluates every preemptor again.  plane, m: as for
+// launch_preempt, the plane written once before the first preemptor; m.rs is 0
+// (the sequential dry run holds no Reservation state).  Nothing synchronises.
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
-                                 int32_t max_victims, bool full, const uint64_t *plane, hipStream_t s);
+                                 int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s);
 
 }  // namespace kh

@@ -9,7 +9,8 @@
 //                     permuted COPY of the records so that a thread's list is
 //                     one contiguous run of 160-B records (no index gather in
 //                     the hot kernel).
-//   k_preempt         256-node tiles x preemptor tiles; the tile's preemptors
+//   k_preempt<NUMA, RS>
+//                     256-node tiles x preemptor tiles; the tile's preemptors
 //                     are staged in LDS, a thread loads its node row once and
 //                     copies it per preemptor.  The walk over a node's list
 //                     diverges, the loop over preemptors does not: per
@@ -23,17 +24,11 @@
 //                     per pair (fails / fails unresolvably), written as one
 //                     ballot word per wave.  The plugin has no
 //                     PreFilterExtensions, so the verdict holds for the whole
-//                     call; the *_n kernels below are the walk reading it.
-//   k_preempt_victims one thread per preemptor re-runs its chosen node and
+//                     call; the NUMA instantiations are the walk reading it.
+//   k_preempt_victims<NUMA, RS>
+//                     one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
-//   k_preempt_r / k_preempt_victims_r <NUMA, RS>
-//                     the same two with Reservation state (KOORDHIP_PREEMPT_RESV):
-//                     the walk starts from the row after the cycle's restore for
-//                     the preemptor and keeps the plugin's AddPod / RemovePod
-//                     state (preemptible, preemptibleInRRs: resv.hpp ResvPre)
-//                     per (preemptor, node) in registers; RS = 1 or
-//                     KOORDHIP_RESV_SLOTS reservation slots per node.
-//   k_preempt_blk / k_preempt_seq / k_preempt_seq_pick / k_preempt_apply
+//   k_preempt_blk<NUMA> / k_preempt_seq<NUMA> / k_preempt_seq_pick / k_preempt_apply<NUMA>
 //                     the sequential dry run (koordhip_preempt_stream): the
 //                     preemptors in input order, each on the state the earlier
 //                     ones left (victims gone, preemptors nominated, budgets
@@ -43,6 +38,16 @@
 //                     evaluate again, one wave picks, one wave re-runs the
 //                     chosen node and applies it.
 //
+// The five walk kernels are templates on what preempt.h's WalkMode says of the
+// call, and with_walk below is the one place a WalkMode becomes template
+// arguments.  NUMA: NodeNUMAResource is in the Filter, the walk reads
+// k_preempt_numa's plane (the kernels that read verdicts take a NumaPlane, empty
+// without NUMA).  RS > 0: Reservation state (KOORDHIP_PREEMPT_RESV): the walk
+// starts from the row after the cycle's restore for the preemptor and keeps
+// the plugin's AddPod / RemovePod state (preemptible, preemptibleInRRs:
+// resv.hpp ResvPre) per (preemptor, node) in registers; RS = 1 or
+// KOORDHIP_RESV_SLOTS reservation slots per node.  Not in the stream.
+//
 // Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
 // reads the row the previous add / remove left), so a wave would hold 63 idle
 // lanes per step; with a thread per node the chain's steps of 64 nodes issue
@@ -50,6 +55,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "diag.h"
 #include "eval.hpp"
@@ -430,6 +436,40 @@ __device__ __forceinline__ uint32_t plane_code(const NumaPlane &pl, int32_t p, i
   return (uint32_t)((row[0] >> b) & 1ull) * NUMA_F_FAIL | (uint32_t)((row[pl.nw] >> b) & 1ull) * NUMA_F_UNRESOLVABLE;
 }
 
+// One node as preempt_node reads it: the row, the walk's NUMA row and the node's listed pods.
+template <int RS>
+struct WalkNode {
+  NV v{};
+  WalkRow<RS> nr{};
+  const DevAsg *list;
+  int32_t len;
+};
+
+// Node i under the envelope c.  live = false: a tail lane, which reads the last row and walks an empty list.
+template <bool NUMA, int RS>
+__device__ __forceinline__ WalkNode<RS> load_walk_node(const DevCfg &c, const DevNodes &d,
+                                                       const DevAsg *__restrict__ tab, const int32_t *__restrict__ off,
+                                                       int32_t i, bool live = true) {
+  const int32_t il = live ? i : d.n - 1;
+  WalkNode<RS> x;
+  const Need all = need_all(c);
+  load_node(x.v, d, il, all, c);
+  load_walk_numa<NUMA, RS>(x.nr, c, d, il, all);
+  const int32_t lo = off[il];
+  x.len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+  x.list = tab + lo;
+  return x;
+}
+
+// The preemptors pre[p0, p0 + np) of a workgroup's tile into LDS, 8-B words over all threads; the caller's
+// __syncthreads() publishes them.
+__device__ __forceinline__ const DevPre *stage_pre(const DevPre *__restrict__ pre, int32_t p0, int32_t np) {
+  __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
+  const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
+  for (int32_t w = threadIdx.x; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
+  return reinterpret_cast<const DevPre *>(spw);
+}
+
 // ---------------------------------------------------------------------------
 // k_preempt_numa
 
@@ -441,14 +481,11 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_numa(DevCfg cfg, De
                                                                   uint64_t *__restrict__ plane, int32_t nw) {
   DevCfg c = cfg;
   c.amp = 0;  // filterAmplifiedCPUs reads the row: it is the walk's
-  __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
   const int t = threadIdx.x, lane = __lane_id();
   const int32_t p0 = (int32_t)blockIdx.y * PRE_PT;
   const int32_t np = min(PRE_PT, n_pre - p0);
-  const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
-  for (int32_t w = t; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
+  const DevPre *sp = stage_pre(pre, p0, np);
   __syncthreads();
-  const DevPre *sp = reinterpret_cast<const DevPre *>(spw);
   const int32_t i = (int32_t)blockIdx.x * PREEMPT_THREADS + t;
   const bool live = i < d.n;
   const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and set no bit
@@ -497,6 +534,51 @@ __device__ __forceinline__ void wave_best(koordhip_preempt_node &r, int32_t &bn)
   }
 }
 
+// One preemptor's vote of a wave: node i's verdict r (live = false: a tail lane, counted nowhere) into the
+// workgroup's status counters cnt [5] (LDS), the wave's best candidate into *best.
+__device__ __forceinline__ void wave_vote(koordhip_preempt_node r, int32_t i, bool live, int32_t *cnt,
+                                          PreemptPartial *best) {
+  const int lane = __lane_id();
+  const int32_t st = live ? r.status : -1;
+#pragma unroll
+  for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
+    const uint64_t mk = __ballot(st == s);
+    if (lane == 0 && mk) atomicAdd(&cnt[s], (int32_t)__popcll(mk));
+  }
+  int32_t bn = st == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
+  wave_best(r, bn);
+  if (lane == 0) {
+    PreemptPartial b{};
+    if (bn >= 0) b.v = r;
+    b.node = bn;
+    *best = b;
+  }
+}
+
+// the workgroup's best candidate of one preemptor: the best of its waves' sb [PRE_WAVES]
+__device__ __forceinline__ PreemptPartial block_best(const PreemptPartial *sb) {
+  PreemptPartial b = sb[0];
+#pragma unroll
+  for (int w = 1; w < PRE_WAVES; w++) {
+    const PreemptPartial x = sb[w];
+    if (pick_before(x.v, x.node, b.v, b.node)) b = x;
+  }
+  return b;
+}
+
+// the answer of one preemptor: its pick (node -1: none) and its nodes per status
+__device__ __forceinline__ koordhip_preempt_result pick_result(const koordhip_preempt_node &best, int32_t node,
+                                                               const int32_t *cnt) {
+  koordhip_preempt_result r{};
+  r.node = node;
+  for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) r.count[s] = cnt[s];
+  if (node >= 0) {
+    r.best = best;
+    r.best.status = KOORDHIP_PREEMPT_CANDIDATE;
+  }
+  return r;
+}
+
 // BLK: the workgroup's counts go to bcnt [n_pre][gridDim.x][5] instead of
 // being summed into count (the sequential dry run replaces single blocks).
 // NUMA: pl holds the frozen verdicts of pre[0, n_pre).  RS: preempt_node's.
@@ -508,61 +590,29 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
                                               koordhip_preempt_node *__restrict__ per_node,
                                               int32_t *__restrict__ bcnt, const NumaPlane &pl) {
   const DevCfg c = envelope<NUMA, RS>(cfg);
-  __shared__ __attribute__((aligned(16))) uint64_t spw[PRE_PT * PRE_WORDS];
   __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_PT][PRE_WAVES];
-  const int t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
+  const int t = threadIdx.x, wave = t >> 6;
   const int32_t p0 = (int32_t)blockIdx.y * PRE_PT;
   const int32_t np = min(PRE_PT, n_pre - p0);
-  const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
-  for (int32_t w = t; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
+  const DevPre *sp = stage_pre(pre, p0, np);
   for (int32_t w = t; w < np * KOORDHIP_PREEMPT_STATUSES; w += PREEMPT_THREADS) scnt[w] = 0;
   __syncthreads();
-  const DevPre *sp = reinterpret_cast<const DevPre *>(spw);
   const int32_t i = (int32_t)blockIdx.x * PREEMPT_THREADS + t;
   const bool live = i < d.n;
-  const int32_t il = live ? i : d.n - 1;  // tail lanes read the last row and count nowhere
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
-  WalkRow<RS> nr{};
-  load_walk_numa<NUMA, RS>(nr, c, d, il, all);
-  const int32_t lo = off[il];
-  const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
-  const DevAsg *list = tab + lo;
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i, live);
   for (int32_t q = 0; q < np; q++) {
     koordhip_preempt_node r{};
     uint32_t fcode = 0u;
     if constexpr (NUMA) fcode = plane_code(pl, p0 + q, i);
     if (live)
-      r = preempt_node<EMIT_NONE, false, NUMA, RS>(c, d.nu.cls, v, nr, list, len, pdb, sp[q], nullptr, 0, NodeOverlay{},
-                                                    fcode);
-    const int32_t st = live ? r.status : -1;
-#pragma unroll
-    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
-      const uint64_t mk = __ballot(st == s);
-      if (lane == 0 && mk) atomicAdd(&scnt[q * KOORDHIP_PREEMPT_STATUSES + s], (int32_t)__popcll(mk));
-    }
+      r = preempt_node<EMIT_NONE, false, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, sp[q], nullptr, 0,
+                                                    NodeOverlay{}, fcode);
     if (per_node && live) per_node[(size_t)q * d.n + i] = r;
-    int32_t bn = st == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
-    wave_best(r, bn);
-    if (lane == 0) {
-      PreemptPartial b{};
-      if (bn >= 0) b.v = r;
-      b.node = bn;
-      sbest[q][wave] = b;
-    }
+    wave_vote(r, i, live, &scnt[q * KOORDHIP_PREEMPT_STATUSES], &sbest[q][wave]);
   }
   __syncthreads();
-  if (t < np) {
-    PreemptPartial b = sbest[t][0];
-#pragma unroll
-    for (int w = 1; w < PRE_WAVES; w++) {
-      const PreemptPartial x = sbest[t][w];
-      if (pick_before(x.v, x.node, b.v, b.node)) b = x;
-    }
-    part[(size_t)(p0 + t) * gridDim.x + blockIdx.x] = b;
-  }
+  if (t < np) part[(size_t)(p0 + t) * gridDim.x + blockIdx.x] = block_best(sbest[t]);
   for (int32_t w = t; w < np * KOORDHIP_PREEMPT_STATUSES; w += PREEMPT_THREADS) {
     const int32_t x = scnt[w];
     if constexpr (BLK) {
@@ -574,61 +624,31 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
   }
 }
 
+// pl: k_preempt_numa's plane for pre[0, n_pre) (NUMA), else empty
+template <bool NUMA, int RS>
 __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
                                                              const int32_t *__restrict__ off, PdbAllowed pdb,
                                                              const DevPre *__restrict__ pre, int32_t n_pre,
                                                              int32_t *__restrict__ count,
                                                              PreemptPartial *__restrict__ part,
-                                                             koordhip_preempt_node *__restrict__ per_node) {
-  preempt_tiles<false, false>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, NumaPlane{});
-}
-
-// ... with NodeNUMAResource in the Filter, reading k_preempt_numa's plane
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                               const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                               const DevPre *__restrict__ pre, int32_t n_pre,
-                                                               int32_t *__restrict__ count,
-                                                               PreemptPartial *__restrict__ part,
-                                                               koordhip_preempt_node *__restrict__ per_node,
-                                                               NumaPlane pl) {
-  preempt_tiles<false, true>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
-}
-
-// ... with Reservation state (KOORDHIP_PREEMPT_RESV): RS reservation slots per node, NUMA as above (pl unused without)
-template <bool NUMA, int RS>
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_r(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                               const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                               const DevPre *__restrict__ pre, int32_t n_pre,
-                                                               int32_t *__restrict__ count,
-                                                               PreemptPartial *__restrict__ part,
-                                                               koordhip_preempt_node *__restrict__ per_node,
-                                                               NumaPlane pl) {
+                                                             koordhip_preempt_node *__restrict__ per_node,
+                                                             NumaPlane pl) {
   preempt_tiles<false, NUMA, RS>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
 }
 
 // Phase 1 of the sequential dry run: one tile of preemptors on the loaded
-// state.  Once the budgets have changed (or with the A/B knob) every block
-// evaluates every later preemptor again and nothing reads this tile: skip it.
+// state (pl: the tile's first preemptor's words).  Once the budgets have
+// changed (or with the A/B knob) every block evaluates every later preemptor
+// again and nothing reads this tile: skip it.
+template <bool NUMA>
 __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_blk(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
                                                                  const int32_t *__restrict__ off, PdbAllowed pdb,
                                                                  const DevPre *__restrict__ pre, int32_t n_pre,
                                                                  PreemptPartial *__restrict__ part,
                                                                  int32_t *__restrict__ bcnt,
-                                                                 const StreamFlags *__restrict__ flags) {
+                                                                 const StreamFlags *__restrict__ flags, NumaPlane pl) {
   if (flags->pdb | flags->full) return;
-  preempt_tiles<true, false>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt, NumaPlane{});
-}
-
-// ... in the NUMA mode (pl: the tile's first preemptor's words)
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_blk_n(DevCfg cfg, DevNodes d,
-                                                                   const DevAsg *__restrict__ tab,
-                                                                   const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                                   const DevPre *__restrict__ pre, int32_t n_pre,
-                                                                   PreemptPartial *__restrict__ part,
-                                                                   int32_t *__restrict__ bcnt,
-                                                                   const StreamFlags *__restrict__ flags, NumaPlane pl) {
-  if (flags->pdb | flags->full) return;
-  preempt_tiles<true, true>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt, pl);
+  preempt_tiles<true, NUMA>(cfg, d, tab, off, pdb, pre, n_pre, nullptr, part, nullptr, bcnt, pl);
 }
 
 // one wave per preemptor over its nb partials
@@ -643,77 +663,27 @@ __global__ __launch_bounds__(64) void k_preempt_pick(const PreemptPartial *__res
     const PreemptPartial x = part[(size_t)p * nb + k];
     if (pick_before(x.v, x.node, b.v, b.node)) b = x;
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    PreemptPartial x{};
-    x.v.n_victims = __shfl_xor(b.v.n_victims, o, 64);
-    x.v.n_pdb_violations = __shfl_xor(b.v.n_pdb_violations, o, 64);
-    x.v.top_priority = __shfl_xor(b.v.top_priority, o, 64);
-    x.v.sum_priority = __shfl_xor((long long)b.v.sum_priority, o, 64);
-    x.v.earliest_start = __shfl_xor((long long)b.v.earliest_start, o, 64);
-    x.node = __shfl_xor(b.node, o, 64);
-    if (pick_before(x.v, x.node, b.v, b.node)) b = x;
-  }
-  if (lane == 0) {
-    koordhip_preempt_result r{};
-    r.node = b.node;
-    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) r.count[s] = count[(size_t)p * KOORDHIP_PREEMPT_STATUSES + s];
-    if (b.node >= 0) {
-      r.best = b.v;
-      r.best.status = KOORDHIP_PREEMPT_CANDIDATE;
-    }
-    res[p] = r;
-  }
+  wave_best(b.v, b.node);
+  if (lane == 0) res[p] = pick_result(b.v, b.node, count + (size_t)p * KOORDHIP_PREEMPT_STATUSES);
 }
 
 // one thread per preemptor: its chosen node again, writing the victims (vout is -1 filled by the caller).
 // NUMA: a chosen node is a CANDIDATE, so its frozen verdict is "passes" and only filterAmplifiedCPUs is left.
-template <bool NUMA, int RS = 0>
-__device__ __forceinline__ void preempt_victims(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
-                                                const int32_t *__restrict__ off, const PdbAllowed &pdb,
-                                                const DevPre *__restrict__ pre, int32_t n_pre,
-                                                const koordhip_preempt_result *__restrict__ res,
-                                                int32_t *__restrict__ vout, int32_t vmax) {
-  const DevCfg c = envelope<NUMA, RS>(cfg);
-  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (p >= n_pre) return;
-  const int32_t i = res[p].node;
-  if (i < 0 || i >= d.n) return;
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, i, all, c);
-  WalkRow<RS> nr{};
-  load_walk_numa<NUMA, RS>(nr, c, d, i, all);
-  const int32_t lo = off[i];
-  const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
-  const DevPre P = pre[p];
-  (void)preempt_node<EMIT_IDX, false, NUMA, RS>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, vout + (size_t)p * vmax, vmax,
-                                                NodeOverlay{}, 0u);
-}
-
+template <bool NUMA, int RS>
 __global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
                                                         const int32_t *__restrict__ off, PdbAllowed pdb,
                                                         const DevPre *__restrict__ pre, int32_t n_pre,
                                                         const koordhip_preempt_result *__restrict__ res,
                                                         int32_t *__restrict__ vout, int32_t vmax) {
-  preempt_victims<false>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
-}
-
-__global__ __launch_bounds__(64) void k_preempt_victims_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                          const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                          const DevPre *__restrict__ pre, int32_t n_pre,
-                                                          const koordhip_preempt_result *__restrict__ res,
-                                                          int32_t *__restrict__ vout, int32_t vmax) {
-  preempt_victims<true>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
-}
-
-template <bool NUMA, int RS>
-__global__ __launch_bounds__(64) void k_preempt_victims_r(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                          const int32_t *__restrict__ off, PdbAllowed pdb,
-                                                          const DevPre *__restrict__ pre, int32_t n_pre,
-                                                          const koordhip_preempt_result *__restrict__ res,
-                                                          int32_t *__restrict__ vout, int32_t vmax) {
-  preempt_victims<NUMA, RS>(cfg, d, tab, off, pdb, pre, n_pre, res, vout, vmax);
+  const DevCfg c = envelope<NUMA, RS>(cfg);
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n_pre) return;
+  const int32_t i = res[p].node;
+  if (i < 0 || i >= d.n) return;
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i);
+  const DevPre P = pre[p];
+  (void)preempt_node<EMIT_IDX, false, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P,
+                                                vout + (size_t)p * vmax, vmax, NodeOverlay{}, 0u);
 }
 
 // ---------------------------------------------------------------------------
@@ -749,11 +719,13 @@ __device__ __forceinline__ DevPre stream_pre(const DevPre *__restrict__ pre, con
 // Block b evaluates preemptor k again iff its rows / lists changed, the
 // budgets changed or k's quota was freed; a block none of this holds for keeps
 // the partial and the counts phase 1 wrote (they depend on nothing else).
+// pl: the plane of all the call's preemptors.
 template <bool NUMA>
-__device__ __forceinline__ void preempt_seq(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
-                                            const int32_t *__restrict__ off, const DevPre *__restrict__ pre, int32_t k,
-                                            const StreamState &st, const NumaPlane &pl) {
-  const int t = threadIdx.x, lane = __lane_id(), wave = t >> 6;
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off,
+                                                                 const DevPre *__restrict__ pre, int32_t k,
+                                                                 StreamState st, NumaPlane pl) {
+  const int t = threadIdx.x, wave = t >> 6;
   const int32_t b = (int32_t)blockIdx.x, nb = (int32_t)gridDim.x;
   const StreamFlags fl = *st.flags;
   if (!(fl.full | fl.pdb | st.qflag[k] | st.touched[b])) {
@@ -770,60 +742,17 @@ __device__ __forceinline__ void preempt_seq(const DevCfg &cfg, const DevNodes &d
   const PdbAllowed pdb = *st.pdb;
   const int32_t i = b * PREEMPT_THREADS + t;
   const bool live = i < d.n;
-  const int32_t il = live ? i : d.n - 1;
-  NV v{};
-  const Need all = need_all(c);
-  load_node(v, d, il, all, c);
-  NumaRowRS<1> nr{};
-  load_walk_numa<NUMA>(nr, c, d, il, all);
-  const int32_t lo = off[il];
-  const int32_t len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, live);
   koordhip_preempt_node r{};
   uint32_t fcode = 0u;
   if constexpr (NUMA) fcode = plane_code(pl, k, i);
   if (live)
-    r = preempt_node<EMIT_NONE, true, NUMA>(c, d.nu.cls, v, nr, tab + lo, len, pdb, P, nullptr, 0, overlay_of(st, il),
-                                            fcode);
-  const int32_t s0 = live ? r.status : -1;
-#pragma unroll
-  for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) {
-    const uint64_t mk = __ballot(s0 == s);
-    if (lane == 0 && mk) atomicAdd(&scnt[s], (int32_t)__popcll(mk));
-  }
-  int32_t bn = s0 == KOORDHIP_PREEMPT_CANDIDATE ? i : -1;
-  wave_best(r, bn);
-  if (lane == 0) {
-    PreemptPartial x{};
-    if (bn >= 0) x.v = r;
-    x.node = bn;
-    sbest[wave] = x;
-  }
+    r = preempt_node<EMIT_NONE, true, NUMA>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, nullptr, 0,
+                                            overlay_of(st, i), fcode);
+  wave_vote(r, i, live, scnt, &sbest[wave]);
   __syncthreads();
-  if (t == 0) {
-    PreemptPartial x = sbest[0];
-#pragma unroll
-    for (int w = 1; w < PRE_WAVES; w++) {
-      const PreemptPartial y = sbest[w];
-      if (pick_before(y.v, y.node, x.v, x.node)) x = y;
-    }
-    st.part[(size_t)k * nb + b] = x;
-  }
+  if (t == 0) st.part[(size_t)k * nb + b] = block_best(sbest);
   if (t < KOORDHIP_PREEMPT_STATUSES) st.bcnt[((size_t)k * nb + b) * KOORDHIP_PREEMPT_STATUSES + t] = scnt[t];
-}
-
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                                 const int32_t *__restrict__ off,
-                                                                 const DevPre *__restrict__ pre, int32_t k,
-                                                                 StreamState st) {
-  preempt_seq<false>(cfg, d, tab, off, pre, k, st, NumaPlane{});
-}
-
-__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq_n(DevCfg cfg, DevNodes d,
-                                                                   const DevAsg *__restrict__ tab,
-                                                                   const int32_t *__restrict__ off,
-                                                                   const DevPre *__restrict__ pre, int32_t k,
-                                                                   StreamState st, NumaPlane pl) {
-  preempt_seq<true>(cfg, d, tab, off, pre, k, st, pl);
 }
 
 // one wave: preemptor k's nb partials and counts -> res[k]
@@ -846,14 +775,7 @@ __global__ __launch_bounds__(64) void k_preempt_seq_pick(int32_t nb, int32_t k, 
   for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++)
     for (int o = 32; o >= 1; o >>= 1) cnt[s] += __shfl_xor(cnt[s], o, 64);
   if (lane == 0) {
-    koordhip_preempt_result out{};
-    out.node = bn;
-    for (int s = 0; s < KOORDHIP_PREEMPT_STATUSES; s++) out.count[s] = cnt[s];
-    if (bn >= 0) {
-      out.best = r;
-      out.best.status = KOORDHIP_PREEMPT_CANDIDATE;
-    }
-    st.res[k] = out;
+    st.res[k] = pick_result(r, bn, cnt);
     if (st.flags->pdb | st.qflag[k]) st.stats->full_recomputes += 1;
   }
 }
@@ -861,33 +783,28 @@ __global__ __launch_bounds__(64) void k_preempt_seq_pick(int32_t nb, int32_t k, 
 // One wave: the chosen node of preemptor k again, its victims written out and
 // taken off the state every later preemptor sees.
 template <bool NUMA>
-__device__ __forceinline__ void preempt_apply(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
-                                              const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
-                                              int32_t n_pre, int32_t k, const StreamState &st, int32_t vmax) {
+__global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                      const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
+                                                      int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
   const DevCfg c = envelope<NUMA>(cfg);
   const int lane = threadIdx.x;
   const int32_t i = st.res[k].node;
   if (i < 0 || i >= d.n) return;
-  const int32_t lo = off[i];
-  const int32_t len = min(off[i + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS);
+  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i);  // i is the wave's: scalar loads
   // the node's list into LDS with the whole wave: lane 0's walk is a chain of dependent loads
   __shared__ uint4 slist[KOORDHIP_PREEMPT_NODE_PODS * ASG_VEC];
-  const uint4 *src = reinterpret_cast<const uint4 *>(tab + lo);
-  for (int32_t w = lane; w < len * ASG_VEC; w += 64) slist[w] = src[w];
+  const uint4 *src = reinterpret_cast<const uint4 *>(nd.list);
+  for (int32_t w = lane; w < nd.len * ASG_VEC; w += 64) slist[w] = src[w];
   __syncthreads();
   const DevAsg *list = reinterpret_cast<const DevAsg *>(slist);
   const DevPre P = stream_pre(pre, st, k);
   __shared__ int32_t sfreed;
   __shared__ int64_t ssum[KOORDHIP_PREEMPT_QRES];
   if (lane == 0) {
-    NV v{};
-    const Need all = need_all(c);
-    load_node(v, d, i, all, c);
-    NumaRowRS<1> nr{};
-    load_walk_numa<NUMA>(nr, c, d, i, all);
     PdbAllowed pdb = *st.pdb;
-    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA>(c, d.nu.cls, v, nr, list, len, pdb, P, st.vpos,
-                                                                       KOORDHIP_PREEMPT_NODE_PODS, overlay_of(st, i), 0u);
+    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA>(c, d.nu.cls, nd.v, nd.nr, list, nd.len, pdb, P,
+                                                                       st.vpos, KOORDHIP_PREEMPT_NODE_PODS,
+                                                                       overlay_of(st, i), 0u);
     const int32_t nv = r.status == KOORDHIP_PREEMPT_CANDIDATE ? min(r.n_victims, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
     uint64_t g0 = 0, g1 = 0;
     int64_t sum[KOORDHIP_PREEMPT_QRES] = {};
@@ -937,18 +854,6 @@ __device__ __forceinline__ void preempt_apply(const DevCfg &cfg, const DevNodes 
   }
 }
 
-__global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                      const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
-                                                      int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
-  preempt_apply<false>(cfg, d, tab, off, pre, n_pre, k, st, vmax);
-}
-
-__global__ __launch_bounds__(64) void k_preempt_apply_n(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
-                                                        const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
-                                                        int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
-  preempt_apply<true>(cfg, d, tab, off, pre, n_pre, k, st, vmax);
-}
-
 // ---------------------------------------------------------------------------
 // host-side launch wrappers
 
@@ -974,14 +879,28 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
 
 size_t preempt_plane_words(int32_t n, int32_t n_pre) { return (size_t)std::max(n_pre, 0) * 2 * (((size_t)n + 63) / 64); }
 
-int preempt_resv_slots(const DevCfg &c) { return c.resv_slots > 1 ? KOORDHIP_RESV_SLOTS : 1; }
+// The launchers' argument check: m is the walk of every state the profile has (the mode with every flag
+// accepted: NodeNUMAResource in the Filter needs the plane, Reservation state the walk with its slots).
+static bool preempt_profile_ok(const DevCfg &c, WalkMode m, const uint64_t *plane) {
+  const WalkMode all = preempt_walk_mode(c, KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV);
+  return m.numa == all.numa && m.rs == all.rs && m.numa == (plane != nullptr);
+}
 
-// NodeNUMAResource in the Filter needs the plane, Reservation state the walk with rs slots (0: none; 1 or
-// KOORDHIP_RESV_SLOTS as the snapshot's resv_slots ask)
-static bool preempt_profile_ok(const DevCfg &c, const uint64_t *plane, int rs = 0) {
-  const bool resv = c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION);
-  if (resv ? rs != preempt_resv_slots(c) : rs != 0) return false;
-  return ((c.filt & KOORDHIP_PLUGIN_NUMA) != 0) == (plane != nullptr);
+// The one place a WalkMode becomes template arguments: f(std::bool_constant<NUMA>, std::integral_constant<int, RS>).
+template <class F>
+static void with_walk(WalkMode m, F f) {
+  auto slots = [&](auto numa) {
+    if (m.rs > 1)
+      f(numa, std::integral_constant<int, KOORDHIP_RESV_SLOTS>{});
+    else if (m.rs == 1)
+      f(numa, std::integral_constant<int, 1>{});
+    else
+      f(numa, std::integral_constant<int, 0>{});
+  };
+  if (m.numa)
+    slots(std::true_type{});
+  else
+    slots(std::false_type{});
 }
 
 hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
@@ -996,92 +915,61 @@ hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre 
 
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
-                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, int rs,
+                          PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, WalkMode m,
                           hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (!preempt_profile_ok(c, plane, rs)) return hipErrorInvalidValue;
+  if (!preempt_profile_ok(c, m, plane)) return hipErrorInvalidValue;
   if (per_node && n_pre != 1) return hipErrorInvalidValue;
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
-  if (rs) {
-    const NumaPlane pl{plane, (d.n + 63) / 64};
-    auto go = [&](auto kernel) {
-      hipLaunchKernelGGL(kernel, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part,
-                         per_node, pl);
-    };
-    if (rs > 1)
-      plane ? go(k_preempt_r<true, KOORDHIP_RESV_SLOTS>) : go(k_preempt_r<false, KOORDHIP_RESV_SLOTS>);
-    else
-      plane ? go(k_preempt_r<true, 1>) : go(k_preempt_r<false, 1>);
-  } else if (plane)
-    hipLaunchKernelGGL(k_preempt_n, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part,
-                       per_node, NumaPlane{plane, (d.n + 63) / 64});
-  else
-    hipLaunchKernelGGL(k_preempt, grid, dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node);
+  const NumaPlane pl{plane, (d.n + 63) / 64};
+  with_walk(m, [&](auto numa, auto rs) {
+    hipLaunchKernelGGL((k_preempt<decltype(numa)::value, decltype(rs)::value>), grid, dim3(PREEMPT_THREADS), 0, s, c, d,
+                       tab, off, pdb, pre, n_pre, count, part, per_node, pl);
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
-                                 int32_t max_victims, bool full, const uint64_t *plane, hipStream_t s) {
+                                 int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (!preempt_profile_ok(c, plane)) return hipErrorInvalidValue;
+  if (m.rs != 0 || !preempt_profile_ok(c, m, plane)) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
   const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
   fl.full = full ? 1 : 0;
   hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, s, pdb, fl, st);
-  for (int32_t k = 0; k < n_pre; k++) {
-    // phase 1 a tile ahead of its first preemptor, not all at once: the loaded state does not change, and a tile
-    // launched after the budgets changed costs an empty kernel
-    if (k % PRE_PT == 0) {
-      if (plane)
-        hipLaunchKernelGGL(k_preempt_blk_n, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
+  with_walk(m, [&](auto numa, auto) {
+    constexpr bool NUMA = decltype(numa)::value;
+    const dim3 blocks(nb), threads(PREEMPT_THREADS), wave(64);
+    for (int32_t k = 0; k < n_pre; k++) {
+      // phase 1 a tile ahead of its first preemptor, not all at once: the loaded state does not change, and a tile
+      // launched after the budgets changed costs an empty kernel
+      if (k % PRE_PT == 0)
+        hipLaunchKernelGGL(k_preempt_blk<NUMA>, blocks, threads, 0, s, c, d, tab, off, pdb, pre + k,
                            std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
                            st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags,
-                           NumaPlane{plane + (size_t)k * 2 * pl.nw, pl.nw});
-      else
-        hipLaunchKernelGGL(k_preempt_blk, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre + k,
-                           std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
-                           st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags);
+                           NUMA ? NumaPlane{plane + (size_t)k * 2 * pl.nw, pl.nw} : pl);
+      hipLaunchKernelGGL(k_preempt_seq<NUMA>, blocks, threads, 0, s, c, d, tab, off, pre, k, st, pl);
+      hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), wave, 0, s, nb, k, st);
+      hipLaunchKernelGGL(k_preempt_apply<NUMA>, dim3(1), wave, 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
     }
-    if (plane)
-      hipLaunchKernelGGL(k_preempt_seq_n, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st, pl);
-    else
-      hipLaunchKernelGGL(k_preempt_seq, dim3(nb), dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pre, k, st);
-    hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), dim3(64), 0, s, nb, k, st);
-    if (plane)
-      hipLaunchKernelGGL(k_preempt_apply_n, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
-    else
-      hipLaunchKernelGGL(k_preempt_apply, dim3(1), dim3(64), 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
-  }
+  });
   return hipGetLastError();
 }
 
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, int rs, hipStream_t s) {
+                               int32_t max_victims, WalkMode m, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
-  if (victims && max_victims > 0) {
-    if (rs) {
-      const bool numa = (c.filt & KOORDHIP_PLUGIN_NUMA) != 0;
-      auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims,
-                           max_victims);
-      };
-      if (rs > 1)
-        numa ? go(k_preempt_victims_r<true, KOORDHIP_RESV_SLOTS>) : go(k_preempt_victims_r<false, KOORDHIP_RESV_SLOTS>);
-      else
-        numa ? go(k_preempt_victims_r<true, 1>) : go(k_preempt_victims_r<false, 1>);
-    } else if (c.filt & KOORDHIP_PLUGIN_NUMA)
-      hipLaunchKernelGGL(k_preempt_victims_n, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre,
-                         res, victims, max_victims);
-    else
-      hipLaunchKernelGGL(k_preempt_victims, dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre,
-                         res, victims, max_victims);
-  }
+  if (victims && max_victims > 0)
+    with_walk(m, [&](auto numa, auto rs) {
+      hipLaunchKernelGGL((k_preempt_victims<decltype(numa)::value, decltype(rs)::value>), dim3((n_pre + 63) / 64),
+                         dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims, max_victims);
+    });
   return hipGetLastError();
 }
 

@@ -9,9 +9,9 @@ In one process, on the same table, alternating per call size:
 
   resv   koordhip_preempt_set_mode(RESV) under the profile with Reservation in
          the Filter: the walk starts from the restored row and keeps the
-         plugin's AddPod / RemovePod state (k_preempt_r<NUMA, slots>)
+         plugin's AddPod / RemovePod state (k_preempt<NUMA, slots>)
   plain  the same profile without the Reservation plugin on the same table:
-         the walk of the default mode (k_preempt / k_preempt_n)
+         the walk of the default mode (k_preempt<NUMA, 0>)
 
 --numa puts NodeNUMAResource into both profiles (both legs set NUMA_FROZEN).
 Each figure is the median of --reps timed calls after --warmup untimed ones;

@@ -67,12 +67,35 @@ def _verdict(status, nv=0, npdb=0, top=0, sump=0, es=0):
     return v
 
 
-def select_victims(cfg, table: NodeTable, assigned: np.ndarray, pdb_allowed, pre: np.ndarray, lists=None):
+class Rule:
+    """What a mode of the dry run adds to the walk, for one preemptor: made by
+    select_victims as rule(cfg, table, pre, rows), where `table` holds the rows
+    the walk starts from and `rows` the hypothetical ones it moves.  This one is
+    the base dry run; preempt_numa_model and preempt_resv_model define theirs."""
+
+    def __init__(self, cfg, table, pre, rows):
+        pass
+
+    def unresolvable(self, i: int) -> bool:
+        """Node i's start row is UNRESOLVABLE although no static filter fails."""
+        return False
+
+    def fits(self, status: int, i: int) -> bool:
+        """The preemptor fits node i's hypothetical row, whose oracle status is `status`."""
+        return status == 0
+
+    def moved(self, i: int, a, sign: int):
+        """Listed pod `a` left (-1) or rejoined (+1) node i's row: what else moves with it."""
+
+
+def select_victims(cfg, table: NodeTable, assigned: np.ndarray, pdb_allowed, pre: np.ndarray, lists=None, rule=Rule):
     """One preemptor on every node: (verdicts [n] PREEMPT_NODE_DTYPE, victims
-    per node as lists of table indices in append order, potential victims per node)."""
+    per node as lists of table indices in append order, potential victims per
+    node; [] where the start row is UNRESOLVABLE)."""
     n = table.n
     lists = lists if lists is not None else node_lists(assigned, n)
     rows = _Rows(cfg, table, pre["pod"])
+    mode = rule(cfg, table, pre, rows)
     verdicts = np.zeros(n, abi.PREEMPT_NODE_DTYPE)
     P_prio, P_quota = int(pre["priority"]), int(pre["quota"])
     st0 = rows.status()
@@ -85,12 +108,14 @@ def select_victims(cfg, table: NodeTable, assigned: np.ndarray, pdb_allowed, pre
     def take(i, j, sign):
         a = assigned[j]
         rows.move(i, a["pod"], sign)
+        mode.moved(i, a, sign)
         if int(a["flags"]) & abi.ASG_IN_QUOTA:
             for d in range(abi.PREEMPT_QRES):
                 used[i][d] = used[i][d] + int(a["qreq"][d]) if sign > 0 else max(0, used[i][d] - int(a["qreq"][d]))
 
     for i in range(n):
-        if st0[i] & abi.ST_STATIC_FAIL:
+        unresolvable = mode.unresolvable(i)
+        if (st0[i] & abi.ST_STATIC_FAIL) or unresolvable:
             verdicts[i] = _verdict(abi.PREEMPT_UNRESOLVABLE)
             done[i] = True
             continue
@@ -114,7 +139,7 @@ def select_victims(cfg, table: NodeTable, assigned: np.ndarray, pdb_allowed, pre
         order[i], nviol[i] = viol + rest, len(viol)
     st1 = rows.status()
     for i in range(n):
-        if not done[i] and st1[i] != 0:
+        if not done[i] and not mode.fits(int(st1[i]), i):
             verdicts[i] = _verdict(abi.PREEMPT_UNFIT)
             done[i] = True
     victims = [[] for _ in range(n)]
@@ -129,7 +154,7 @@ def select_victims(cfg, table: NodeTable, assigned: np.ndarray, pdb_allowed, pre
         st = rows.status()
         for i in live:
             j = order[i][step]
-            fits = st[i] == 0
+            fits = mode.fits(int(st[i]), i)
             if not fits:
                 take(i, j, -1)
                 victims[i].append(j)
@@ -181,14 +206,14 @@ def pick(verdicts: np.ndarray):
     return res
 
 
-def dry_run(cfg, table, assigned, pdb_allowed, pres):
+def dry_run(cfg, table, assigned, pdb_allowed, pres, rule=Rule):
     """All preemptors: (results [p], verdicts [p][n], chosen victims per preemptor, victims / potential per (p, node))."""
     lists = node_lists(assigned, table.n)
     res = np.zeros(len(pres), abi.PREEMPT_RESULT_DTYPE)
     ver = np.zeros((len(pres), table.n), abi.PREEMPT_NODE_DTYPE)
     chosen, allv, allp = [], [], []
     for p in range(len(pres)):
-        v, vic, pot = select_victims(cfg, table, assigned, pdb_allowed, pres[p], lists)
+        v, vic, pot = select_victims(cfg, table, assigned, pdb_allowed, pres[p], lists, rule)
         ver[p] = v
         res[p] = pick(v)
         chosen.append(vic[int(res[p]["node"])] if res[p]["node"] >= 0 else [])

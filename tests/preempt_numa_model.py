@@ -6,8 +6,8 @@ preempt_model.select_victims already evaluates every hypothetical row with the
 full oracle, the NodeNUMAResource Filter and filterAmplifiedCPUs included, and
 moves only the row columns: the free-CPU masks, the allocated cpuset count and
 the zone amounts stay as loaded, which is the plugin without
-PreFilterExtensions.  What this module adds is step 1: a node whose FIRST
-failing plugin on the row the walk starts from holds an
+PreFilterExtensions.  What this module adds is step 1, as the walk's NumaRule:
+a node whose FIRST failing plugin on the row the walk starts from holds an
 UnschedulableAndUnresolvable reason is UNRESOLVABLE (upstream
 nodesWherePreemptionMightHelp reads that plugin's code), found with
 reasons_model.masks and abi.first_reasons.
@@ -17,7 +17,6 @@ two of three preemptors cpuset pods, ~15 % of the nodes with room beside their
 listed pods so that NodeResourcesFit passes and NodeNUMAResource decides) and
 two hand-worked cases, `amp` and `frozen`.
 """
-import contextlib
 import functools
 from unittest import mock
 
@@ -34,7 +33,6 @@ import preempt_model as M
 import preempt_stream_model as S
 import reasons_model as R
 
-_base_select = M.select_victims
 LOOSE_FRAC = 0.15
 
 
@@ -45,31 +43,23 @@ def unresolvable(cfg, table: NodeTable, pod: np.ndarray) -> np.ndarray:
     return (abi.first_reasons(mask) & np.uint32(abi.REASON_UNRESOLVABLE_MASK)) != 0
 
 
-def select_victims(cfg, table, assigned, pdb_allowed, pre, lists=None):
-    """preempt_model.select_victims with step 1 of the NUMA mode.  `table` holds the rows the walk starts from."""
-    ver, vic, pot = _base_select(cfg, table, assigned, pdb_allowed, pre, lists)
-    for i in np.flatnonzero(unresolvable(cfg, table, pre["pod"])):
-        ver[i] = M._verdict(abi.PREEMPT_UNRESOLVABLE)
-        vic[i] = []
-    return ver, vic, pot
+class NumaRule(M.Rule):
+    """Step 1 of the NUMA mode; the fit test and a move are the base walk's."""
 
+    def __init__(self, cfg, table, pre, rows):
+        self.unres = unresolvable(cfg, table, pre["pod"])
 
-@contextlib.contextmanager
-def numa_rule():
-    """preempt_model / preempt_stream_model evaluate with this module's select_victims."""
-    with mock.patch.object(M, "select_victims", select_victims):
-        yield
+    def unresolvable(self, i):
+        return bool(self.unres[i])
 
 
 def dry_run(cfg, table, assigned, pdb_allowed, pres):
-    with numa_rule():
-        return M.dry_run(cfg, table, assigned, pdb_allowed, pres)
+    return M.dry_run(cfg, table, assigned, pdb_allowed, pres, NumaRule)
 
 
 def stream(cfg, table, assigned, pdb_allowed, pres):
-    """preempt_stream_model.stream's loop over select_victims above."""
-    with numa_rule():
-        return S.stream(cfg, table, assigned, pdb_allowed, pres)
+    """preempt_stream_model.stream under NumaRule."""
+    return S.stream(cfg, table, assigned, pdb_allowed, pres, rule=NumaRule)
 
 
 # ---------------------------------------------------------------- generators

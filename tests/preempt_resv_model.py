@@ -11,9 +11,9 @@ on small dict records, so that the reference's own test tables
 table side (slots_of, node_state) restates the BeforePreFilter restore
 (transformer.go:85-175) on a NodeTable's resv_* columns.
 
-select_victims is preempt_model's walk with that state: every "does the
-preemptor fit" is the oracle's status of the hypothetical row without its
-Reservation bit, and filter_with_reservations on the state the walk has reached.
+ResvRule gives preempt_model's walk that state: every "does the preemptor fit"
+is the oracle's status of the hypothetical row without its Reservation bit,
+and filter_with_reservations on the state the walk has reached.
 UNRESOLVABLE follows the diagnosis: on the row the walk starts from, the first
 failing plugin in abi.FILTER_ORDER holds an UnschedulableAndUnresolvable reason.
 
@@ -25,7 +25,6 @@ stores it; the tests use it to show that the quirk decides verdicts.
 Also the generated cases the GPU tests run and four hand-worked ones
 (`restricted`, `default`, `unmatched` with its three nodes, `quirk`).
 """
-import contextlib
 import functools
 from unittest import mock
 
@@ -255,136 +254,53 @@ def without_reservation(table: NodeTable, d_requested, d_npods) -> NodeTable:
     return t
 
 
-def select_victims(cfg, table, assigned, pdb_allowed, pre, lists=None, literal=True, base_cfg=None):
-    """preempt_model.select_victims with the Reservation state.  base_cfg: the
-    profile without the Reservation plugin (for the start rows' reasons)."""
-    n = table.n
-    lists = lists if lists is not None else M.node_lists(assigned, n)
-    pod = pod_record(pre["pod"])
-    rows = M._Rows(cfg, table, pre["pod"])
-    info = [node_state(table, i, pod) for i in range(n)]
-    alloc = [[int(table[f"alloc{k}"][i]) for k in range(NRES)] for i in range(n)]
-    alloc_pods = [int(table["alloc_pods"][i]) for i in range(n)]
-    state = [PreState() for _ in range(n)]
-    resv_on = bool(int(cfg.filter_plugins) & abi.PLUGIN_RESERVATION)
+class ResvRule(M.Rule):
+    """The walk with the Reservation state of every node.  literal: add_pod's;
+    base_cfg: the profile without the Reservation plugin (for the start rows'
+    reasons).  Carried as functools.partial(ResvRule, literal=..., base_cfg=...)."""
 
-    def resv_reason(i):
-        if not resv_on:
+    def __init__(self, cfg, table, pre, rows, literal=True, base_cfg=None):
+        n = table.n
+        self.rows, self.literal = rows, literal
+        self.pod = pod_record(pre["pod"])
+        self.info = [node_state(table, i, self.pod) for i in range(n)]
+        self.alloc = [[int(table[f"alloc{k}"][i]) for k in range(NRES)] for i in range(n)]
+        self.alloc_pods = [int(table["alloc_pods"][i]) for i in range(n)]
+        self.state = [PreState() for _ in range(n)]
+        self.resv_on = bool(int(cfg.filter_plugins) & abi.PLUGIN_RESERVATION)
+        # the first failing plugin of the start row: Fit / LoadAware / NodeNUMAResource by their reasons, then Reservation
+        start = without_reservation(table, np.array([x[2] for x in self.info], np.int64),
+                                    np.array([x[3] for x in self.info], np.int32))
+        mask = R.masks(oracle.Oracle(base_cfg if base_cfg is not None else cfg, start),
+                       np.ascontiguousarray(pre["pod"].reshape(1)))[0]
+        self.first = abi.first_reasons(mask)
+
+    def resv_reason(self, i):
+        if not self.resv_on:
             return None
-        nrs, matched, _, dn = info[i]
-        node = {"alloc": alloc[i], "alloc_pods": alloc_pods[i], "npods": int(rows.cols["npods"][i]) + dn}
-        return filter_with_reservations(pod, node, nrs, matched, state[i])
+        nrs, matched, _, dn = self.info[i]
+        node = {"alloc": self.alloc[i], "alloc_pods": self.alloc_pods[i], "npods": int(self.rows.cols["npods"][i]) + dn}
+        return filter_with_reservations(self.pod, node, nrs, matched, self.state[i])
 
-    def fits(st, i):
-        return (int(st[i]) & ~abi.ST_RESV_FAIL) == 0 and resv_reason(i) is None
+    def unresolvable(self, i):
+        if self.first[i]:
+            return bool(self.first[i] & abi.REASON_UNRESOLVABLE_MASK)
+        return self.resv_reason(i) == "affinity"
 
-    verdicts = np.zeros(n, abi.PREEMPT_NODE_DTYPE)
-    P_prio, P_quota = int(pre["priority"]), int(pre["quota"])
-    st0 = rows.status()
-    # the first failing plugin of the start row: Fit / LoadAware / NodeNUMAResource by their reasons, then Reservation
-    start = without_reservation(table, np.array([x[2] for x in info], np.int64), np.array([x[3] for x in info], np.int32))
-    mask = R.masks(oracle.Oracle(base_cfg if base_cfg is not None else cfg, start), np.ascontiguousarray(pre["pod"].reshape(1)))[0]
-    first = abi.first_reasons(mask)
-    used = [[int(x) for x in pre["q_used"]] for _ in range(n)]
-    done = np.zeros(n, bool)
-    pot = [[] for _ in range(n)]
-    order = [[] for _ in range(n)]
-    nviol = [0] * n
+    def fits(self, status, i):
+        """The oracle's status without its Reservation bit, and filter_with_reservations on the state the walk has reached."""
+        return (status & ~abi.ST_RESV_FAIL) == 0 and self.resv_reason(i) is None
 
-    def take(i, j, sign):
-        a = assigned[j]
-        rows.move(i, a["pod"], sign)
+    def moved(self, i, a, sign):
         req = [int(x) for x in a["pod"]["req"]]
         if sign < 0:
-            remove_pod(state[i], req, bound_slot(a))
+            remove_pod(self.state[i], req, bound_slot(a))
         else:
-            add_pod(state[i], req, bound_slot(a), literal)
-        if int(a["flags"]) & abi.ASG_IN_QUOTA:
-            for d in range(abi.PREEMPT_QRES):
-                used[i][d] = used[i][d] + int(a["qreq"][d]) if sign > 0 else max(0, used[i][d] - int(a["qreq"][d]))
-
-    for i in range(n):
-        unresolvable = bool(first[i] & abi.REASON_UNRESOLVABLE_MASK) if first[i] else resv_reason(i) == "affinity"
-        if (st0[i] & abi.ST_STATIC_FAIL) or unresolvable:
-            verdicts[i] = M._verdict(abi.PREEMPT_UNRESOLVABLE)
-            done[i] = True
-            continue
-        allowed = [int(x) for x in pdb_allowed]
-        viol, rest = [], []
-        for j in lists[i]:
-            a = assigned[j]
-            if (int(a["flags"]) & abi.ASG_NONPREEMPTIBLE) or not int(a["priority"]) < P_prio or int(a["quota"]) != P_quota:
-                continue
-            pot[i].append(j)
-            take(i, j, -1)
-            bad = False
-            for b in range(len(allowed)):
-                if (int(a["pdb_mask"]) >> b) & 1:
-                    allowed[b] -= 1
-                    bad = bad or allowed[b] < 0
-            (viol if bad else rest).append(j)
-        if not pot[i]:
-            verdicts[i] = M._verdict(abi.PREEMPT_NO_VICTIMS)
-            done[i] = True
-        order[i], nviol[i] = viol + rest, len(viol)
-    st1 = rows.status()
-    for i in range(n):
-        if not done[i] and not fits(st1, i):
-            verdicts[i] = M._verdict(abi.PREEMPT_UNFIT)
-            done[i] = True
-    victims = [[] for _ in range(n)]
-    npdb = [0] * n
-    step = 0
-    while True:
-        live = [i for i in range(n) if not done[i] and step < len(order[i])]
-        if not live:
-            break
-        for i in live:
-            take(i, order[i][step], +1)
-        st = rows.status()
-        for i in live:
-            j = order[i][step]
-            ok = fits(st, i)
-            if not ok:
-                take(i, j, -1)
-                victims[i].append(j)
-                if step < nviol[i]:
-                    npdb[i] += 1
-            over = P_quota >= 0 and any((int(pre["q_mask"]) >> d) & 1 and
-                                        used[i][d] + int(pre["q_req"][d]) > int(pre["q_runtime"][d])
-                                        for d in range(abi.PREEMPT_QRES))
-            if over:
-                if not ok:
-                    verdicts[i] = M._verdict(abi.PREEMPT_ERROR)
-                    victims[i] = []
-                    done[i] = True
-                    continue
-                take(i, j, -1)
-                victims[i].append(j)
-        step += 1
-    for i in range(n):
-        if done[i]:
-            continue
-        v = victims[i]
-        if not v:
-            verdicts[i] = M._verdict(abi.PREEMPT_CANDIDATE)
-            continue
-        pr = [int(assigned["priority"][j]) for j in v]
-        top = max(pr)
-        es = min(int(assigned["start_time"][j]) for j in v if int(assigned["priority"][j]) == top)
-        verdicts[i] = M._verdict(abi.PREEMPT_CANDIDATE, len(v), npdb[i], pr[0], sum(p + (1 << 31) for p in pr), es)
-    return verdicts, victims, pot
-
-
-@contextlib.contextmanager
-def resv_rule(literal=True, base_cfg=None):
-    with mock.patch.object(M, "select_victims", functools.partial(select_victims, literal=literal, base_cfg=base_cfg)):
-        yield
+            add_pod(self.state[i], req, bound_slot(a), self.literal)
 
 
 def dry_run(cfg, table, assigned, pdb_allowed, pres, literal=True, base_cfg=None):
-    with resv_rule(literal, base_cfg):
-        return M.dry_run(cfg, table, assigned, pdb_allowed, pres)
+    return M.dry_run(cfg, table, assigned, pdb_allowed, pres, functools.partial(ResvRule, literal=literal, base_cfg=base_cfg))
 
 
 # ---------------------------------------------------------------- generators
@@ -394,6 +310,7 @@ CASES = {
     "wave": (130, 5, M.SEED + 32, 1, False, False),
     "tiles": (257, 33, M.SEED + 34, 4, True, False),
     "numa": (130, 6, M.SEED + 36, 1, False, True),
+    "numa4": (130, 4, M.SEED + 38, 4, False, True),
 }
 GROUPS = 4
 BOUND_FRAC = 0.5

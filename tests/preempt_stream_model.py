@@ -33,9 +33,9 @@ import preempt_model as M
 BLOCK = 256   # nodes per workgroup of the engine's evaluation (the unit of its skip)
 
 
-def stream(cfg, table, assigned, pdb_allowed, pres, lists=None):
+def stream(cfg, table, assigned, pdb_allowed, pres, lists=None, rule=M.Rule):
     """(results [p] PREEMPT_RESULT_DTYPE, full victim lists per preemptor,
-    stats dict) of the preemptors processed in input order."""
+    stats dict) of the preemptors processed in input order.  rule: select_victims'."""
     n = table.n
     lists = lists if lists is not None else M.node_lists(assigned, n)
     nb = (n + BLOCK - 1) // BLOCK
@@ -79,7 +79,7 @@ def stream(cfg, table, assigned, pdb_allowed, pres, lists=None):
                 stats["block_recomputes"] += len(touched)
                 stats["blocks_skipped"] += nb - len(touched)
             stats["quota_flags"] += bool(qflag)
-        ver, vic, _ = M.select_victims(cfg, t, assigned, allowed, pre, lists_k)
+        ver, vic, _ = M.select_victims(cfg, t, assigned, allowed, pre, lists_k, rule)
         res[k] = M.pick(ver)
         c = int(res[k]["node"])
         if c < 0:

@@ -43,10 +43,11 @@ changes the winner of the contests of that row and column:
                                    every shuffle offset carries a winner, in
                                    both directions; all 64 bits of sum and
                                    start by the half and sign contests
-  workgroup LDS (sbest)            */lanes/*: lanes 63 | 64, adjacent waves
+  workgroup LDS (block_best)       */lanes/*: lanes 63 | 64, adjacent waves
   partials, strided loop           */strided/*: workgroups b and b + 64 meet in
                                    one lane on the loop's second trip
-  partials, 64-lane shuffle        */groups/* (nodes 255 | 256, adjacent
+  partials, 64-lane shuffle        (k_preempt_pick's wave_best)
+                                   */groups/* (nodes 255 | 256, adjacent
                                    lanes), */far/* (workgroups 1 and 33: shuffle
                                    offset 32 alone), start/ragged/hi
                                    (workgroups 0 and 65: the winner is the one

@@ -53,7 +53,8 @@ def expect(code, call):
 @pytest.mark.parametrize("name", V.ALL_CASES)
 def test_node_verdicts(Engine, name):
     """One lane; two waves and a partial one; a second node tile and a second
-    preemptor tile on four slots with lists past 64 pods; the shipped profile."""
+    preemptor tile on four slots with lists past 64 pods; the shipped profile
+    on one slot and on four (k_preempt<true, 4>, k_preempt_victims<true, 4>)."""
     m = V.case(name)
     picks = sorted({0, len(m.pres) // 2, len(m.pres) - 1})
     with loaded(Engine, m) as e:

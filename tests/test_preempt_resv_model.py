@@ -138,7 +138,7 @@ def test_generated_cases_meet_the_coverage_conditions():
                    "restricted_insufficient", "restricted_passes_returned", "restricted_insufficient_returned",
                    "insufficient", "matched_passes"):
         assert taken.get(branch, 0) > 0, branch
-    for name in ("wave", "tiles", "numa"):
+    for name in ("wave", "tiles", "numa", "numa4"):
         counts = cases[name].res["count"].sum(axis=0)
         assert (counts > 0).all(), (name, counts)                               # every status occurs
         assert (cases[name].res["count"].sum(axis=1) == cases[name].table.n).all()
