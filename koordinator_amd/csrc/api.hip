@@ -2291,6 +2291,7 @@ kh::PlaceKnobs read_place_knobs() {
   k.SHARD_LOCAL_SIM = on("KOORDHIP_SHARD_LOCAL_SIM"), k.SHARD_FORCE = on("KOORDHIP_SHARD_FORCE");
   k.LAG1 = on("KOORDHIP_LAG1"), k.LAG2 = on("KOORDHIP_LAG2"), k.EXT_SEQ = on("KOORDHIP_EXT_SEQ");
   k.CHAIN_OFF = on("KOORDHIP_CHAIN_OFF"), k.STAMPS = on("KOORDHIP_STAMPS");
+  k.SAMECLS_OFF = on("KOORDHIP_SAMECLS_OFF");
   k.NO_PRELOAD = on("KOORDHIP_NO_PRELOAD"), k.NO_KEY_TABLES = on("KOORDHIP_NO_KEY_TABLES");
   k.EXT_LEAD = num("KOORDHIP_EXT_LEAD", k.EXT_LEAD);
   k.CHAIN_PASSES = num("KOORDHIP_CHAIN_PASSES", k.CHAIN_PASSES);
@@ -2780,7 +2781,9 @@ int begin_call(koordhip_ctx *c, PlaceCall *pc) {
 // k_resolve over the rounds [r0, r1) on stream s (M' handed between launches in d_mod)
 int launch_resolve_rounds(koordhip_ctx *c, const PlaceCall &pc, int32_t r0, int32_t r1, int32_t mono, int32_t lag,
                           hipStream_t s) {
-  HIP_TRY(kh::launch_resolve(c->dc, c->d, c->d_desc, c->d_pods, c->n_staged, pc.plan.P, pc.plan.K, r0, r1,
+  // (the staged pods' classes: the resolve's same-class speculation; none when the batch has too many)
+  const int32_t *pod_cls = c->cls_rep.empty() ? nullptr : c->d_pod_cls;
+  HIP_TRY(kh::launch_resolve(c->dc, c->d, c->d_desc, c->d_pods, pod_cls, c->n_staged, pc.plan.P, pc.plan.K, r0, r1,
                              pc.plan.exch ? c->d_final : c->d_lists, (int64_t)kListBuf, mono, lag, pc.sync, c->d_mod,
                              c->d_out, c->d_cpus, c->d_dbg, pc.knobs.TRACE_POD, pc.knobs.NO_PRELOAD,
                              pc.knobs.NO_KEY_TABLES, s));
@@ -3012,6 +3015,13 @@ int print_stamps(koordhip_ctx *c, const kh::PlacePlan &plan) {
                  "claim table %llu\n", (unsigned long long)h[62],
                  (unsigned long long)h[63], (unsigned long long)q[0], (unsigned long long)q[1],
                  (unsigned long long)q[2], (unsigned long long)q[3], (unsigned long long)rw[7]);
+    uint64_t sp[7] = {0, 0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpy(sp, c->d_dbg + 116, sizeof(sp), hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[koordhip stamps] same-class speculation: made %llu  validated %llu  invalidated %llu | "
+                 "given up: no head row %llu  walk past the entries %llu  winner assumed-claimed %llu  winner row in "
+                 "HBM %llu\n", (unsigned long long)sp[0], (unsigned long long)sp[1], (unsigned long long)sp[2],
+                 (unsigned long long)sp[3], (unsigned long long)sp[4], (unsigned long long)sp[5],
+                 (unsigned long long)sp[6]);
   }
   if (plan.ext_pipe) {
     uint64_t q[8];

@@ -1391,6 +1391,9 @@ __global__ __launch_bounds__(ETK_THREADS) __attribute__((amdgpu_waves_per_eu(NM 
 // first entry outside M' -- that walk is the pod's decision if no earlier pod
 // of the round commits to a node it walked (its "examined" set E).  The
 // winner's row is staged (list-head prefetch, M' row, or one HBM load).
+// A pod with earlier pods of its class in the round (plain build, monotone)
+// walks on instead, past the entries it assumes they take, and its decision
+// then depends on their commits (same-class speculation, below at spec_on).
 // Loop (wave 0, s_setprio 3): pod l takes its staged decision unless E meets
 // M (one LDS gather of E against the M bitmap + a ballot) or the pod is
 // non-monotone / a cpuset pod; those take the general path (c, then every M
@@ -1446,6 +1449,10 @@ struct ResLds {  // byte offsets into the dynamic LDS of k_resolve
   // resolves the previous round (overlap = 0: every round loads serially)
   int32_t overlap, lists2, pods2, pre_rows2, pre_numa2, pre_node2;
   int32_t ptab;  // the column-pointer table (res_ptab_bytes), -1: none
+  // per pod of the round, one u64: byte 0 = its rank among the round's pods of
+  // its class (earlier same-class pods), bytes 1-7 = those pods' indices in
+  // pod order (the first RES_WE - 1); rank2: the next round's copy.  -1: none
+  int32_t rank, rank2;
 };
 
 __host__ __device__ inline int32_t res_align(int32_t x) { return (x + 15) & ~15; }
@@ -1508,6 +1515,9 @@ __host__ __device__ inline ResLds res_lds(int32_t n_pods_max, int32_t kp, int32_
   at += RES_MAXP_ROUND * 4;
   o.dep = chain ? at : -1;
   at += chain ? RES_MAXP_ROUND * 8 : 0;
+  o.rank = chain ? at : -1;  // (with the chained decisions only: the Reservation builds have no byte to spare)
+  at += chain ? RES_MAXP_ROUND * 8 : 0;
+  o.rank2 = o.rank;
   o.moved = at;  // per M' slot: committed to again this round (its row moved into M)
   at += RES_MAXP_ROUND * 4;
   o.mhash = at;  // lazy staged rows: the pod of each M slot, the M slot of each pod
@@ -1548,6 +1558,10 @@ __host__ __device__ inline ResLds res_lds(int32_t n_pods_max, int32_t kp, int32_
     at += numa ? res_align(RES_PRE * nrow) : 0;
     o.pre_node2 = at;
     at += RES_PRE * 4;
+    if (chain) {
+      o.rank2 = at;
+      at += RES_MAXP_ROUND * 8;
+    }
   }
   o.total = at;
   return o;
@@ -1578,6 +1592,7 @@ __global__ void k_wait_resolved(PipeSync *sy, int32_t rounds) {
 template <int NM, bool DBG>
 __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const DevNodes *__restrict__ dn, int32_t n_nodes,
                                                                  const DevNumaClass *__restrict__ ncls, const DevPod *__restrict__ pods,
+                                                                 const int32_t *__restrict__ pod_cls,
                                                                  int32_t total, int32_t P, int32_t k, int32_t kp,
                                                                  int32_t r_begin, int32_t r_end,
                                                                  int32_t *__restrict__ mbuf,
@@ -1677,6 +1692,20 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   }
   const bool two = kp > 64;
   const bool chain_on = (monotone & 2) && ofs.dep >= 0;  // the chained decisions (phase 2c)
+  // Same-class speculation (phase 1): a pod with earlier pods of its class in
+  // the round assumes that they take the first entries outside X of the list
+  // they share, in order, and stages the decision that follows from that; 2b
+  // checks the assumption against the claims.  The plain build with the
+  // chained decisions and the staged pods' classes only (monotone bit 4,
+  // KOORDHIP_SAMECLS_OFF, turns it off).  Wave 1 computes the ranks while it
+  // loads a round (load_round), nothing on wave 0's path does; the first
+  // round of a launch has none and runs without.  The one-launch-per-round
+  // path (every round is a first round, and its monotone argument has no
+  // chain bit) runs with this off.
+  static_assert(RES_WE == 8, "a pod's rank word: one rank byte + RES_WE - 1 predecessor bytes");
+  const bool spec_on = NM == 0 && chain_on && ofs.rank >= 0 && pod_cls != nullptr && !(monotone & 16);
+  uint64_t *rk = reinterpret_cast<uint64_t *>(lds + (ofs.rank >= 0 ? ofs.rank : 0));
+  uint64_t *rk2 = reinterpret_cast<uint64_t *>(lds + (ofs.rank2 >= 0 ? ofs.rank2 : 0));
   const uint64_t t_kernel = (dbg && t == 0) ? stamp() : 0;
   if (t == 0) {
     sh_mp = r_begin > 0 ? min(mbuf[0], P) : 0;
@@ -1747,6 +1776,9 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   uint64_t c_rw[4] = {0, 0, 0, 0}, n_chbm = 0;             // ... re-walks: walk + keys, winners' rows; chain HBM row loads
   uint64_t n_lazy = 0;                               // rounds whose final claim table was built (by the loop's first claimer())
   uint64_t c_ext = 0, n_ext = 0;                     // device pods: cycles from the hand-off to the worker's answer, pods
+  // same-class speculation: decisions made, validated, invalidated (2b or the closure), given up for: no head
+  // row, a walk past RES_WE (or the list's end), the winner an assumed-claimed node, the winner's row in HBM:
+  // dbg[116 .. 122], added where they happen (rare events: no running counters kept in registers)
   // ---- a round's global reads: lists -> LDS (stride kp, zero padded), pod
   //      records, and the rows of each pod's first HP list entries (slot HP j + q)
   // Two dependent HBM round trips (wave 1..3 run this for the next round, and
@@ -1760,10 +1792,18 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
   //      entries; A's LDS stores sit between B's issue and its wait.
   // Lists longer than one batch (one loader wave, or a large P x k) stream
   // through a loop that issues batch i + 1 before batch i's stores wait.
+  // Same-class speculation (Rk, spec_on): lane j < rn of wave 1 -- the first
+  // loader wave, and the second wave of a load that every wave runs -- also
+  // reads pod j's class id in trip A and, after everything else, writes the
+  // pod's rank word (ResLds::rank): its rank among the round's pods of its
+  // class and those predecessors.  Nothing on wave 0's path computes ranks.
   auto load_round = [&](int32_t rr, int32_t rp0, int32_t rn, uint64_t *Lk, DevPod *Lp, NV *Pr, NR *Pn,
-                        int32_t *Pnode, int32_t tid, int32_t nth) {
+                        int32_t *Pnode, uint64_t *Rk, int32_t tid, int32_t nth) {
     const uint64_t *L = lists0 + (size_t)(rr & (2 * lag - 1)) * list_buf;
     const int32_t tot = rn * k;  // >= 1: a round has a pod, a list an entry
+    const int32_t rl = t - 64;  // lane of wave 1 (rn <= 64)
+    int32_t mycls = -1;
+    if (Rk && rl >= 0 && rl < rn) mycls = pod_cls[rp0 + rl];
     // ---- trip A
     uint64_t he[2] = {0, 0};
     bool hv[2];
@@ -1880,6 +1920,18 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       }
       Pnode[sl] = n1;
     }
+    if (Rk && rl >= 0 && rl < 64) {  // (wave-uniform: wave 1)
+      uint64_t w = 0;
+      int32_t cnt = 0;
+      for (int32_t j = 0; j < rn; j++) {
+        const int32_t cj = __builtin_amdgcn_readlane(mycls, j);  // (uniform j: no LDS crossbar)
+        if (j < rl && cj == mycls) {
+          if (cnt < RES_WE - 1) w |= (uint64_t)j << (8 * (cnt + 1));
+          cnt++;
+        }
+      }
+      if (rl < rn) Rk[rl] = w | (uint64_t)cnt;
+    }
   };
   auto prev_slot = [&](int32_t nd) -> int32_t {
     uint32_t h = res_hash(nd);
@@ -1903,7 +1955,16 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
     if (sh_stop) return;  // the evaluation side failed: give up, the host reports it
     const uint64_t t_entry = (dbg && t == 0) ? stamp() : 0;
     const int32_t mp = sh_mp;
-    if (!preloaded) load_round(r, p0, n_pods, lk, lpod, pre, prenr, pre_node, t, RES_THREADS);
+    if (!preloaded) {
+      // (the first round of a launch has no rank words -- no round before it
+      // during which the loader waves could have computed them -- and runs
+      // without the same-class speculation, whichever layout the launch has;
+      // without the preload every later round's ranks come from wave 1 here)
+      const bool first = r == r_begin;
+      load_round(r, p0, n_pods, lk, lpod, pre, prenr, pre_node, (spec_on && !first) ? rk : nullptr, t, RES_THREADS);
+      if (spec_on && first)
+        for (int32_t x = t; x < n_pods; x += RES_THREADS) rk[x] = 0ull;
+    }
     for (int32_t x = t; x < RES_HASH; x += RES_THREADS) hnode[x] = -1;
     if (t == 0) {
       sh_done = 0;
@@ -1940,14 +2001,61 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       const uint32_t bz = (uint32_t)(__ballot(live && e == 0) >> g) & 0xFFu;
       const int f = bx ? __builtin_ctz(bx) : RES_WE, z = bz ? __builtin_ctz(bz) : RES_WE;
       const bool general = f == RES_WE && z == RES_WE;  // RES_WE M' entries in a row
-      const bool walked = live && !general && (q < min(f, z) || (q == f && f < z));
+      // ---- same-class speculation: a pod of rank i - 1 > 0 (monotone, not a
+      //      device pod) assumes that its i - 1 same-class predecessors take the
+      //      first i - 1 entries outside X, in order.  Its walk then runs to
+      //      the i-th entry outside X (fw, exact); lane (l, q) still evaluates
+      //      one entry: an X entry on its M' row, an assumed-claimed entry on
+      //      the pod's own head row + its own Reserve delta (the same class:
+      //      the claimer's record and delta), or the exact entry's list key.
+      //      Given up -- the plain walk, which conflicts as it always did -- when
+      //      the walk would pass RES_WE entries or the list's end, an assumed
+      //      entry has no head row, the winner is an assumed-claimed node (two
+      //      commits to one node) or the winner's row would need the HBM load
+      //      into the pod's first head slot, which an assumed entry may own.
+      bool spec = false;
+      int fw = f, gu = -1;  // the entry that ends the walk; DBG: why speculation was given up
+      uint64_t rkw = 0;
+      if constexpr (NM == 0) {
+        if (spec_on) {
+          rkw = live ? rk[l] : 0ull;
+          const int rank = (int)(rkw & 0xFFull);
+          if (rank > 0 && !(lpod[l].flags & KH_POD_EXT)) {
+            uint32_t b = bx;
+            for (int u = 0; u < rank && b; u++) b &= b - 1u;
+            if (rank < RES_WE && b && __builtin_ctz(b) < z) {
+              spec = true;
+              fw = __builtin_ctz(b);
+            } else {
+              gu = 1;
+            }
+          }
+          if (__ballot(spec)) {
+            const bool nohead = spec && q < fw && !inx && !(q < HP && pre_node[l * HP + q] == nd);
+            if (spec && ((uint32_t)(__ballot(nohead) >> g) & 0xFFu)) {
+              spec = false;
+              fw = f;
+              gu = 0;
+            }
+          }
+        }
+      }
+      bool walked = live && !general && (q < min(fw, z) || (q == fw && fw < z));
+      bool assumed = spec && q < fw && !inx;  // (an entry below fw is in X or assumed-claimed)
       uint64_t key = 0;
       int32_t ms = -1;
       if (walked) {
-        if (q < min(f, z)) {  // an M' entry: its exact key on the current row
-          ms = prev_slot(nd);
+        if (q < min(fw, z)) {
           const DevPod pod = lpod[l];
-          key = make_key(eval_row<NM>(pod, slot_row(prow[ms]), pnr[ms], cls, c), nd);
+          NV v;
+          if (assumed) {  // the row its claimer commits to
+            v = pre[l * HP + q];
+            apply_delta(v, pod, +1);
+          } else {  // an M' entry: its exact key on the current row
+            ms = prev_slot(nd);
+            v = slot_row(prow[ms]);
+          }
+          key = make_key(eval_row<NM>(pod, v, pnr[ms >= 0 ? ms : 0], cls, c), nd);
         } else {
           key = e;
         }
@@ -1957,6 +2065,31 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       for (int m = 1; m < RES_WE; m <<= 1) {
         const uint64_t o = shfl_xor_u64(mx, m);
         mx = o > mx ? o : mx;
+      }
+      if constexpr (NM == 0) {
+        if (__ballot(spec)) {  // (wave-uniform)
+          const bool win = spec && walked && key == mx && mx != 0;
+          const uint32_t brep = (uint32_t)(__ballot(win && assumed) >> g) & 0xFFu;
+          const uint32_t bhbm =
+              (uint32_t)(__ballot(win && q == fw && !(q < HP && pre_node[l * HP + q] == nd)) >> g) & 0xFFu;
+          const bool back = spec && (brep | bhbm) != 0u;
+          if (back) {  // the plain walk: the M' entries above f keep their keys
+            spec = false;
+            gu = brep ? 2 : 3;
+            fw = f;
+            assumed = false;
+            walked = q < min(f, z) || (q == f && f < z);
+            key = walked ? (q == f ? e : key) : 0ull;
+          }
+          if (__ballot(back)) {
+            mx = key;
+#pragma unroll
+            for (int m = 1; m < RES_WE; m <<= 1) {
+              const uint64_t o = shfl_xor_u64(mx, m);
+              mx = o > mx ? o : mx;
+            }
+          }
+        }
       }
       if (live) {
         dec_e[l * RES_WE + q] = walked ? nd : -1;
@@ -1986,9 +2119,26 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
           dec_src[l] = src;
         }
         if (q == 0) {
-          const int32_t dn = general ? -1 : (f < z ? f + 1 : z);
+          const int32_t dn = general ? -1 : (fw < z ? fw + 1 : z);
           dec_key[l] = mx;
           dec_n[l] = dn;
+          // the staged commits the decision assumed (none: a plain walk); the
+          // chained decisions and the loop's voiding read them
+          if (ofs.dep >= 0) {
+            uint64_t dm = 0;
+            if (spec)
+              for (int u = 1; u <= (int)(rkw & 0xFFull); u++) dm |= 1ull << ((rkw >> (8 * u)) & 0xFFull);
+            reinterpret_cast<uint64_t *>(lds + ofs.dep)[l] = dm;
+          }
+          if constexpr (NM == 0) {
+            // byte 0 of the rank word from here on: the assumed-claimed entries
+            // among the walked ones (2b), in list order = predecessor order
+            if (spec_on) rk[l] = (rkw & ~0xFFull) | (spec ? (uint64_t)(bx & ((1u << fw) - 1u)) : 0ull);
+            if (dbg) {
+              if (spec) atomicAdd((unsigned long long *)&dbg[116], 1ull);
+              if (gu >= 0) atomicAdd((unsigned long long *)&dbg[119 + gu], 1ull);
+            }
+          }
           if (mx == 0 || dn < 0) dec_src[l] = 0;
           // "slow" pods always take the general path: a non-monotone configuration,
           // NUMA cpuset pods (Allocate at Reserve; required-policy feasibility is
@@ -2034,22 +2184,35 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       const int32_t l = x / RES_WE;
       const int32_t y = dec_e[x];
       if (y >= 0 && !(dec_c[l] & 2)) {
+        int32_t cv = 64;  // y's first claimer
         uint32_t h = res_hash(y);
         for (;;) {
           const int32_t xk = ckey[h];
           if (xk == y) {
-            if (cval[h] < l) atomicOr(&dec_c[l], 1);
+            cv = cval[h];
             break;
           }
           if (xk < 0) break;
           h = (h + 1) & (RES_HASH - 1);
         }
+        // an assumed-claimed entry is consistent iff its first claimer is the
+        // predecessor the walk assumed there; any other walked entry conflicts
+        // iff an earlier pod claims it
+        bool bad = cv < l;
+        if constexpr (NM == 0) {
+          if (spec_on) {
+            const uint64_t w = rk[l];
+            const uint32_t am = (uint32_t)(w & 0xFFull);
+            const int32_t q = x - l * RES_WE;
+            if ((am >> q) & 1u) bad = cv != (int32_t)((w >> (8 * (1 + __popc(am & ((1u << q) - 1u))))) & 0xFFull);
+          }
+        }
+        if (bad) atomicOr(&dec_c[l], 1);
       }
     }
     __syncthreads();
+    // (phase 1 wrote every pod's dep: the commits its staged decision assumed)
     uint64_t *dep = ofs.dep >= 0 ? reinterpret_cast<uint64_t *>(lds + ofs.dep) : nullptr;
-    if (dep)
-      for (int32_t x = t; x < n_pods; x += RES_THREADS) dep[x] = 0ull;
     if (dbg && t == 0) {
       const uint64_t t_p3 = stamp();
       c_hash += t_a - t_entry;
@@ -2109,6 +2272,30 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       };
       if (chain_on) {
         const uint64_t t_c0 = dbg ? stamp() : 0;
+        if constexpr (NM == 0) {
+          // same-class speculation: 2b checked each decision's own entries; the
+          // closure in pod order, as after a chain pass -- a pod that assumed a
+          // conflicting predecessor's commit conflicts too
+          if (spec_on) {
+            const bool lv = lane < n_pods;
+            const uint64_t dl = lv ? dep[lane] : 0ull;
+            const uint64_t made = __ballot(dl != 0ull);
+            if (made) {
+              uint64_t valid = __ballot(lv && dec_c[lane] == 0);
+              for (;;) {
+                const uint64_t bad = __ballot(((valid >> lane) & 1ull) && (dl & ~valid) != 0ull);
+                if (!bad) break;
+                valid &= ~bad;
+                if ((bad >> lane) & 1ull) dec_c[lane] = 1;
+              }
+              wsync();
+              if (dbg && lane == 0) {
+                atomicAdd((unsigned long long *)&dbg[117], (unsigned long long)__popcll(made & valid));
+                atomicAdd((unsigned long long *)&dbg[118], (unsigned long long)__popcll(made & ~valid));
+              }
+            }
+          }
+        }
         auto claimer_of = [&](int32_t y) -> int32_t {
           uint32_t q = res_hash(y);
           for (;;) {
@@ -2121,9 +2308,11 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
         // the first pass's claims from 2b's table (every non-slow pod's staged
         // winner -> its first claimer): drop the nodes whose first claimer
         // conflicts -- every later claimer of such a node met that claim on its
-        // own walk (its winner is a walked entry), so it conflicts too, and the
-        // table then holds exactly the valid pods' claims (a tombstone, -2,
-        // keeps the probe chains)
+        // own walk (its winner is a walked entry, and never an assumed-claimed
+        // one: a speculative walk that would win one is given up), so it
+        // conflicts too -- the closure above included -- and the table then
+        // holds exactly the valid pods' claims (a tombstone, -2, keeps the
+        // probe chains)
         auto drop_conflicting = [&]() {
           if (lane < n_pods && dec_c[lane] == 1 && dec_key[lane] != 0ull) {
             const int32_t y = key_node(dec_key[lane]);
@@ -2844,7 +3033,8 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
         if (lane == 0) ok = wait_at_least(&sy->sel[(r + 1) & 1], P * ((r + 1) >> 1) + np2, sy) ? 1 : 0;
         const uint64_t t2 = dbg ? stamp() : 0;
         if (__builtin_amdgcn_readfirstlane(ok)) {
-          load_round(r + 1, p0 + P, np2, lk2, lpod2, pre2, prenr2, pre_node2, t - 64, 64 * res_loaders<NM>());
+          load_round(r + 1, p0 + P, np2, lk2, lpod2, pre2, prenr2, pre_node2, spec_on ? rk2 : nullptr, t - 64,
+                     64 * res_loaders<NM>());
           if (dbg) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             c_w1load += stamp() - t2;
@@ -2917,6 +3107,9 @@ __global__ __launch_bounds__(res_threads<NM>()) void k_resolve(DevCfg c, const D
       int32_t *e2 = pre_node;
       pre_node = pre_node2;
       pre_node2 = e2;
+      uint64_t *f2 = rk;
+      rk = rk2;
+      rk2 = f2;
     }
     {  // M's rows become the next round's M' rows
       NV *x = prow;
@@ -3311,7 +3504,8 @@ int32_t resolve_lds_bytes(int32_t n_pods_max, int32_t k, int32_t n_nodes, int nm
   return res_lds(n_pods_max, kp, n_nodes, side_row_bytes(nm), false, false, lag, false, nm <= 2).total;
 }
 
-hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_desc, const DevPod *pods, int32_t total, int32_t P, int32_t k,
+hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_desc, const DevPod *pods, const int32_t *pod_cls,
+                          int32_t total, int32_t P, int32_t k,
                           int32_t r_begin, int32_t r_end, const uint64_t *lists0, int64_t list_buf, int32_t monotone,
                           int32_t lag, PipeSync *sync, int32_t *mbuf, int32_t *out_node, uint64_t *out_cpus, uint64_t *dbg,
                           int32_t trace, bool no_preload, bool no_key_tables, hipStream_t s) {
@@ -3356,7 +3550,7 @@ hipError_t launch_resolve(const DevCfg &c, const DevNodes &d, const DevNodes *d_
   do {                                                                                                        \
     note_kernel(g_resolve_name, DD ? "kh::k_resolve<%d, true>" : "kh::k_resolve<%d, false>", NN);                \
     hipLaunchKernelGGL((k_resolve<NN, DD>), dim3(1), dim3(res_threads<NN>()), o.total, s, c, d_desc, d.n, d.nu.cls, \
-                       pods, total, P, k, kp, r_begin, r_end, mbuf, lists0, list_buf, monotone, lag, sync, o, out_node, \
+                       pods, pod_cls, total, P, k, kp, r_begin, r_end, mbuf, lists0, list_buf, monotone, lag, sync, o, out_node, \
                        out_cpus, dbg, trace);                                                                   \
   } while (0)
 #define KH_RESOLVE(NN)       \

@@ -33,6 +33,7 @@ struct PlaceKnobs {
   bool SERIAL = false, ROUND_LAUNCH = false, ONE_EVAL_STREAM = false, CLS_OFF = false;
   bool SHARD_LOCAL_SIM = false, SHARD_FORCE = false, LAG1 = false, LAG2 = false;
   bool EXT_SEQ = false, CHAIN_OFF = false, STAMPS = false;
+  bool SAMECLS_OFF = false;  // the resolve's same-class speculation off (A/B)
   bool NO_PRELOAD = false, NO_KEY_TABLES = false;  // the resolve's launcher (kernels.hip launch_resolve)
   int32_t EXT_LEAD = 0;       // unset: 0 (the lead is never below the lag)
   int32_t CHAIN_PASSES = 1;   // unset: 1
@@ -66,7 +67,7 @@ struct PlacePlan {
   bool cls = false;         // class-incremental lists instead of per-round evaluations
   int32_t lag = 1, P = 1, K = 2, rounds = 0;
   int32_t lead = 1;         // device pods: rounds a pre-evaluation runs ahead of its hand-off
-  int32_t mono = 0;         // the persistent resolve's monotone argument (bit 0 | chain bit 1 | passes bits 2-3)
+  int32_t mono = 0;         // the persistent resolve's monotone argument (bit 0 | chain bit 1 | passes bits 2-3 | same-class speculation off bit 4)
   int32_t tstride = 1;      // profile_kernels: every tstride-th round is timed
   int err = 0;              // nonzero: refuse the call with msg (an invalid argument)
   const char *msg = nullptr;
@@ -177,7 +178,11 @@ inline PlacePlan plan_place(const PlaceFacts &f, const PlaceKnobs &k) {
   // 57.11-57.23 ms, three lines each -- two passes win by 0.9 %, more than the
   // lines' spread; the default stays 1 until the plan's hand-worked rows move
   // with it, profiles/r08a_config4_ab.txt)
-  p.mono = f.monotone | ((f.monotone && !k.CHAIN_OFF) ? 2 : 0) | (f.monotone ? ((k.CHAIN_PASSES & 3) << 2) : 0);
+  // (bit 4, SET to turn it off so the default values above stay: the same-class
+  // speculation of the prologue -- a round's pods of one class decided
+  // together, k_resolve phase 1; KOORDHIP_SAMECLS_OFF for A/B)
+  p.mono = f.monotone | ((f.monotone && !k.CHAIN_OFF) ? 2 : 0) | (f.monotone ? ((k.CHAIN_PASSES & 3) << 2) : 0) |
+           ((f.monotone && k.SAMECLS_OFF) ? 16 : 0);
   // profile_kernels: event pairs around the evaluation launches of at most
   // ~256 evenly spaced rounds (the per-kernel averages need no more; every
   // outstanding timed event holds a runtime signal, and a host thread that
