@@ -913,6 +913,8 @@ int koordhip_node_reasons_ext(koordhip_ctx *ctx, const koordhip_pod *pod, const 
 
 #define KOORDHIP_ASG_NONPREEMPTIBLE 1u /* extension.IsPodNonPreemptible */
 #define KOORDHIP_ASG_IN_QUOTA 2u       /* quotaInfo.IsPodExist: the quota's used moves with the pod (plugin.go:302-305) */
+/* bit 2 (4u) is the library's own (it marks the records koordhip_preempt_load_pods_ext gave a non-empty
+ * koordhip_assigned_ext): a caller's bit there is ignored. */
 /* bits 8-11 of flags: the reservation slot of ITS NODE the pod is bound to (its
  * reservation-allocated annotation), read in the KOORDHIP_PREEMPT_RESV mode
  * only.  A field value of 0 means not bound. */
@@ -1090,7 +1092,77 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *
  * KOORDHIP_EINVAL like an unknown bit and leaves the mode as it was: such a
  * context can never hold Reservation state. */
 #define KOORDHIP_PREEMPT_RESV 2u
+/* ---- the dry run under DeviceShare (additive to ABI 15: detect it by the symbols below)
+ * KOORDHIP_PREEMPT_DEVICE lets koordhip_preempt, koordhip_preempt_node_verdicts
+ * and their _ext forms accept a profile whose sequential-cycle plugins are
+ * DeviceShare only (the NodeAffinity / TaintToleration normalized Scores may be
+ * present: the dry run reads no Score).  The plugin has PreFilterExtensions
+ * (deviceshare/plugin.go:184-282): RemovePod adds the victim's device
+ * allocation to preemptibleDevices[node], AddPod subtracts it again, Filter
+ * (:284-323) hands the map to the allocator, which frees it per minor
+ * (device_cache.go:316-365, calcFreeWithPreemptible :454-482).  A victim's
+ * extended scalars leave NodeInfo.Requested.ScalarResources through
+ * NodeInfo.RemovePod, which NodeResourcesFit reads.  Per (preemptor P, node):
+ *   row         also xrequested[j] of the scalars in P's xmask.
+ *   RemovePod   of a listed pod: the row as before, xrequested[j] -= its xreq[j],
+ *               and, when P has KOORDHIP_PODX_DEVICE, the node has a nodeDevice
+ *               entry and the pod holds devices, Pd[t][s] += dev_per[t] for every
+ *               slot s of its dev_slots[t].  AddPod is the reverse
+ *               (SubtractWithNonNegativeResult per minor, a zero entry deleted,
+ *               the difference stored: device_resources.go:65-104).  A pod is
+ *               added back only after it was removed, so no clamp triggers and
+ *               Pd is the sum over the pods removed at the moment.
+ *   fit test    the mode's test, xfit on the moved xrequested, and for a device
+ *               preemptor on a nodeDevice node the DeviceShare Filter with the
+ *               free amounts of slot s of type t taken as
+ *               max0(total - max0(used - Pd)); the rest as in the cycle
+ *               (fillGPUTotalMem per node, calcDeviceWanted, a device counts if
+ *               its free vector is non-zero and holds the per-card request,
+ *               count >= wanted per requested type, a missing type fails).
+ * LoadAware's columns do not move.  XFIT and DEVICE reasons are Unschedulable,
+ * so UNRESOLVABLE keeps its rule and equals koordhip_diagnose_reasons_ext's
+ * `unresolvable`.  Device pods' cpusets stay frozen under
+ * KOORDHIP_PREEMPT_NUMA_FROZEN, which combines with this flag.
+ * On a profile without DeviceShare (Filter or Score) a word with this bit is
+ * KOORDHIP_EINVAL like an unknown bit and leaves the mode as it was.  Still
+ * KOORDHIP_EINVAL with the flag set: PodTopologySpread or InterPodAffinity in
+ * the profile (AddPod / RemovePod state of their own); any Reservation state
+ * (the plugin in the Filter or Score, reservation columns, resv_dev_slot
+ * columns), with or without KOORDHIP_PREEMPT_RESV: that combination needs
+ * preemptibleInRRs and tryAllocateFromReservation and is not built;
+ * koordhip_preempt_stream (gone victims' devices and scalars would have to
+ * leave the call-scoped overlay); what koordhip_preempt refuses besides. */
+#define KOORDHIP_PREEMPT_DEVICE 4u
 int koordhip_preempt_set_mode(koordhip_ctx *ctx, uint32_t flags);
+
+/* What a listed pod holds beyond its koordhip_pod, one record per koordhip_assigned
+ * (parallel arrays).  Quantities in [0, 2^45). */
+typedef struct koordhip_assigned_ext {
+  int64_t xreq[KOORDHIP_NXRES]; /* its extended scalars in NodeInfo.Requested (moved by NodeInfo.RemovePod / AddPod) */
+  int64_t dev_per[KOORDHIP_DEV_TYPES][KOORDHIP_DEV_RES]; /* the amount it holds on EACH of its minors of a type
+                                                          * (every allocated minor holds the per-card request,
+                                                          * plugin.go:465-478) */
+  uint32_t dev_slots[KOORDHIP_DEV_TYPES]; /* bit s: device slot s of its node (koordhip_fetch_devices' convention) */
+  uint32_t xmask;                         /* bit j: xreq[j] is present */
+  uint64_t reserved;
+} koordhip_assigned_ext;
+/* koordhip_preempt_load_pods with the second table; ax == NULL is that call.
+ * KOORDHIP_EINVAL, checked before anything else and leaving the loaded table
+ * in place: a dev_slots bit at or above the snapshot's dev_slots, device
+ * amounts on a context without device columns, a quantity out of range, an
+ * xmask bit past KOORDHIP_NXRES. */
+int koordhip_preempt_load_pods_ext(koordhip_ctx *ctx, const koordhip_assigned *a, const koordhip_assigned_ext *ax,
+                                   int32_t n_assigned, const int32_t *pdb_allowed, int32_t n_pdb);
+/* koordhip_preempt / koordhip_preempt_node_verdicts with the preemptors'
+ * koordhip_pod_ext records (ext[p] beside pre[p]; NULL: all empty, which is the
+ * plain call: state.skip makes the plugin's three hooks no-ops,
+ * plugin.go:197,247,289).  Only dev_req, xreq, xmask and KOORDHIP_PODX_DEVICE
+ * are read; a record with spread or affinity fields set is KOORDHIP_EINVAL, and
+ * so is a non-NULL ext outside the KOORDHIP_PREEMPT_DEVICE mode. */
+int koordhip_preempt_ext(koordhip_ctx *ctx, const koordhip_preemptor *pre, const koordhip_pod_ext *ext, int32_t n_pre,
+                         koordhip_preempt_result *out, int32_t *victims, int32_t max_victims);
+int koordhip_preempt_node_verdicts_ext(koordhip_ctx *ctx, const koordhip_preemptor *pre, const koordhip_pod_ext *ext,
+                                       koordhip_preempt_node *per_node);
 
 /* ---- sequential preemption dry run (additive to ABI 15: detect it by the symbol)
  * The same dry run for a batch whose answers have to hold together: the

@@ -337,6 +337,7 @@ PREEMPT_CANDIDATE, PREEMPT_NO_VICTIMS, PREEMPT_UNFIT, PREEMPT_ERROR, PREEMPT_UNR
 PREEMPT_STATUSES = 5
 PREEMPT_NUMA_FROZEN = 1   # koordhip_preempt_set_mode: NodeNUMAResource in the Filter, its verdict frozen for the call
 PREEMPT_RESV = 2          # ... Reservation state: the walk keeps the plugin's AddPod / RemovePod state
+PREEMPT_DEVICE = 4        # ... DeviceShare: the victims' extended scalars and devices move in the walk
 ASSIGNED_DTYPE = np.dtype([
     ("pod", POD_DTYPE), ("node", "<i4"), ("priority", "<i4"), ("start_time", "<i8"), ("quota", "<i4"),
     ("flags", "<u4"), ("pdb_mask", "<u4"), ("reserved", "<u4"), ("qreq", "<i8", (PREEMPT_QRES,)),
@@ -353,6 +354,12 @@ PREEMPT_RESULT_DTYPE = np.dtype([("node", "<i4"), ("count", "<i4", (PREEMPT_STAT
                                 align=True)
 assert (ASSIGNED_DTYPE.itemsize, PREEMPTOR_DTYPE.itemsize, PREEMPT_NODE_DTYPE.itemsize,
         PREEMPT_RESULT_DTYPE.itemsize) == (160, 208, 32, 56)
+# koordhip_assigned_ext (160 bytes), one per ASSIGNED_DTYPE record: the extended scalars and devices a listed pod holds
+ASSIGNED_EXT_DTYPE = np.dtype([
+    ("xreq", "<i8", (NXRES,)), ("dev_per", "<i8", (DEV_TYPES, DEV_RES)), ("dev_slots", "<u4", (DEV_TYPES,)),
+    ("xmask", "<u4"), ("reserved", "<u8"),
+], align=True)
+assert ASSIGNED_EXT_DTYPE.itemsize == 160
 # koordhip_preempt_stream_stats (24 bytes) of the sequential dry run
 PREEMPT_STREAM_STATS_DTYPE = np.dtype([("full_recomputes", "<i8"), ("block_recomputes", "<i8"), ("blocks_skipped", "<i8")],
                                       align=True)
@@ -402,7 +409,8 @@ _lib = None
 # additive to ABI 15 (no version bump): a build without them still loads
 ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext", "koordhip_diagnose_reasons",
                     "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
-                    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext", "koordhip_preempt_set_mode")
+                    "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext", "koordhip_preempt_set_mode",
+                    "koordhip_preempt_load_pods_ext", "koordhip_preempt_ext", "koordhip_preempt_node_verdicts_ext")
 
 
 def load_library(path: str = LIB_PATH):
@@ -463,6 +471,9 @@ def load_library(path: str = LIB_PATH):
         "koordhip_preempt_node_verdicts": (C.c_int, [vp, vp, vp]),
         "koordhip_preempt_stream": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32, vp]),
         "koordhip_preempt_set_mode": (C.c_int, [vp, C.c_uint32]),
+        "koordhip_preempt_load_pods_ext": (C.c_int, [vp, vp, vp, C.c_int32, _i32p, C.c_int32]),
+        "koordhip_preempt_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
+        "koordhip_preempt_node_verdicts_ext": (C.c_int, [vp, vp, vp, vp]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -503,6 +514,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext",
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_preempt_stream", "koordhip_preempt_set_mode",
+    "koordhip_preempt_load_pods_ext", "koordhip_preempt_ext", "koordhip_preempt_node_verdicts_ext",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

@@ -276,6 +276,12 @@ struct koordhip_ctx {
   void *d_pre_plane = nullptr;     // the frozen NUMA verdicts of one dry-run call (kh::launch_preempt_numa)
   size_t pre_raw_cap = 0, pre_tab_cap = 0, pre_ws_cap = 0, pre_in_cap = 0, pre_out_cap = 0, pre_st_cap = 0;
   size_t pre_plane_cap = 0;
+  void *d_pre_xraw = nullptr;      // the second table (kh::DevAsgX) in input order, and permuted (the DEVICE mode)
+  void *d_pre_xtab = nullptr;
+  void *d_pre_px = nullptr;        // the preemptors' koordhip_pod_ext records of one dry-run call (the DEVICE mode)
+  size_t pre_xraw_cap = 0, pre_xtab_cap = 0, pre_px_cap = 0;
+  bool pre_has_x = false;          // the loaded table has a second table (some record of it is not empty)
+  bool pre_any_device = false;     // some preemptor of the uploaded call has KOORDHIP_PODX_DEVICE
   uint32_t pre_mode = 0;           // koordhip_preempt_set_mode's flags: the context's, not the snapshot's
 };
 
@@ -1247,7 +1253,7 @@ int koordhip_destroy(koordhip_ctx *c) {
                   (void *)c->d_cls_pod, (void *)c->d_cls_buf, (void *)c->d_cls_meta, c->d_cls_S,
                   (void *)c->d_plan, (void *)c->d_plan_pods, (void *)c->d_ext_idx, c->d_ext_scr, c->d_diag_ws,
                   c->d_diag_rec, c->d_diag_pods, c->d_diagx_podx, c->d_diagx_ws, c->d_pre_raw, c->d_pre_tab, c->d_pre_ws, c->d_pre_in, c->d_pre_out,
-                  c->d_pre_st, c->d_pre_plane})
+                  c->d_pre_st, c->d_pre_plane, c->d_pre_xraw, c->d_pre_xtab, c->d_pre_px})
     if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++)
     if (c->ev_res[i]) (void)hipEventDestroy(c->ev_res[i]);
@@ -3623,16 +3629,53 @@ int koordhip_node_reasons_ext(koordhip_ctx *c, const koordhip_pod *pod, const ko
 
 constexpr int64_t kQuotaLimit = 1ll << 53;  // quota amounts: sums of 128 of them and one more stay far inside int64
 
-int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int32_t n_assigned, const int32_t *pdb_allowed,
-                               int32_t n_pdb) {
+constexpr int64_t kDevQtyLimit = 1ll << 45;  // device and extended-scalar quantities, as everywhere else
+
+// The second table's own checks (before anything of the context changes: a refused one leaves the loaded table
+// answering).  *any: some record is not empty.
+static int check_assigned_ext(const koordhip_ctx *c, const koordhip_assigned_ext *ax, int32_t m, bool *any) {
+  const char *who = "koordhip_preempt_load_pods_ext: assigned pod ";
+  *any = false;
+  const int32_t slots = c->d.dv.slots;
+  for (int32_t j = 0; j < m; j++) {
+    const koordhip_assigned_ext &x = ax[j];
+    if (x.xmask >> KOORDHIP_NXRES) return fail(KOORDHIP_EINVAL, who + std::to_string(j) + ": xmask bit past KOORDHIP_NXRES");
+    bool held = x.xmask != 0u;
+    for (int k = 0; k < KOORDHIP_NXRES; k++)
+      if (x.xreq[k] < 0 || x.xreq[k] >= kDevQtyLimit)
+        return fail(KOORDHIP_EINVAL, who + std::to_string(j) + ": xreq outside [0, 2^45)");
+    for (int t = 0; t < KOORDHIP_DEV_TYPES; t++) {
+      bool amount = false;
+      for (int r = 0; r < KOORDHIP_DEV_RES; r++) {
+        if (x.dev_per[t][r] < 0 || x.dev_per[t][r] >= kDevQtyLimit)
+          return fail(KOORDHIP_EINVAL, who + std::to_string(j) + ": dev_per outside [0, 2^45)");
+        amount = amount || x.dev_per[t][r] != 0;
+      }
+      if ((x.dev_slots[t] || amount) && slots <= 0)
+        return fail(KOORDHIP_EINVAL, who + std::to_string(j) + " holds devices and the snapshot has no device columns");
+      if (slots < 32 && (x.dev_slots[t] >> std::max(slots, 0)) != 0u)
+        return fail(KOORDHIP_EINVAL, who + std::to_string(j) + ": dev_slots bit at or above the snapshot's dev_slots");
+      held = held || x.dev_slots[t] != 0u;
+    }
+    *any = *any || held;
+  }
+  return 0;
+}
+
+int koordhip_preempt_load_pods_ext(koordhip_ctx *c, const koordhip_assigned *a, const koordhip_assigned_ext *ax,
+                                   int32_t n_assigned, const int32_t *pdb_allowed, int32_t n_pdb) {
   static_assert(sizeof(koordhip_assigned) == 160 && sizeof(koordhip_preemptor) == 208 &&
-                    sizeof(koordhip_preempt_node) == 32 && sizeof(koordhip_preempt_result) == 56,
+                    sizeof(koordhip_preempt_node) == 32 && sizeof(koordhip_preempt_result) == 56 &&
+                    sizeof(koordhip_assigned_ext) == 160,
                 "preemption records");
   if (!c || (!a && n_assigned > 0) || (!pdb_allowed && n_pdb > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (!c->loaded) return fail(KOORDHIP_ESTATE, "no snapshot loaded");
   if (n_assigned < 0 || n_pdb < 0) return fail(KOORDHIP_EINVAL, "n_assigned / n_pdb < 0");
   if (n_pdb > KOORDHIP_PREEMPT_PDBS)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: more than KOORDHIP_PREEMPT_PDBS (8) PodDisruptionBudgets");
+  bool has_x = false;
+  if (ax)
+    if (int e = check_assigned_ext(c, ax, n_assigned, &has_x)) return e;
   c->pre_loaded = false;
   const int32_t n = c->n, m = n_assigned;
   std::vector<kh::DevPod> hp;
@@ -3653,7 +3696,7 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: assigned pod " + std::to_string(j) +
                                        " has a pdb_mask bit at or above n_pdb");
     if (s.quota < 0) return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: an assigned pod's quota id is >= 0");
-    if (s.flags & ~(KOORDHIP_ASG_NONPREEMPTIBLE | KOORDHIP_ASG_IN_QUOTA | KOORDHIP_ASG_RESV_SLOT_MASK))
+    if (s.flags & ~(KOORDHIP_ASG_NONPREEMPTIBLE | KOORDHIP_ASG_IN_QUOTA | KOORDHIP_ASG_RESV_SLOT_MASK | kh::ASG_HAS_EXT))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_load_pods: unknown koordhip_assigned.flags bit");
     // the reservation slot the pod is bound to: read only with reservation columns (whether the slot is present on
     // the node is not checked: the reference keys the state by UID and does not care either)
@@ -3674,7 +3717,11 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
     }
     o.prio = s.priority;
     o.quota = s.quota;
-    o.flags = flags;
+    o.flags = flags & ~kh::ASG_HAS_EXT;
+    if (has_x) {
+      const koordhip_assigned_ext &x = ax[j];
+      if (x.xmask || x.dev_slots[0] || x.dev_slots[1] || x.dev_slots[2]) o.flags |= kh::ASG_HAS_EXT;
+    }
     o.pdb_mask = s.pdb_mask;
     o.idx = j;
     o.node = s.node;
@@ -3685,9 +3732,18 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
   if (int e = ensure(c, &c->d_pre_tab, &c->pre_tab_cap, tb)) return e;
   if (int e = ensure(c, &c->d_pre_ws, &c->pre_ws_cap, kh::preempt_ws_ints(n, m) * sizeof(int32_t))) return e;
   if (m > 0) HIP_TRY(hipMemcpyAsync(c->d_pre_raw, raw.data(), tb, hipMemcpyHostToDevice, c->stream));
+  has_x = has_x && m > 0;
+  if (has_x) {  // the second table: the caller's records as they are (the layouts agree), permuted with the first
+    static_assert(sizeof(kh::DevAsgX) == sizeof(kh::DevAsg), "one size for both tables");
+    if (int e = ensure(c, &c->d_pre_xraw, &c->pre_xraw_cap, tb)) return e;
+    if (int e = ensure(c, &c->d_pre_xtab, &c->pre_xtab_cap, tb)) return e;
+    HIP_TRY(hipMemcpyAsync(c->d_pre_xraw, ax, tb, hipMemcpyHostToDevice, c->stream));
+  }
   HIP_TRY(kh::launch_preempt_lists(static_cast<const kh::DevAsg *>(c->d_pre_raw), static_cast<kh::DevAsg *>(c->d_pre_tab),
-                                   m, n, static_cast<int32_t *>(c->d_pre_ws), c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // raw is the host's
+                                   m, n, static_cast<int32_t *>(c->d_pre_ws), c->stream,
+                                   has_x ? c->d_pre_xraw : nullptr, has_x ? c->d_pre_xtab : nullptr));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // raw and ax are the host's
+  c->pre_has_x = has_x;
   c->pre_pdb = kh::PdbAllowed{};
   for (int32_t b = 0; b < n_pdb; b++) c->pre_pdb.a[b] = pdb_allowed[b];
   c->pre_m = m;
@@ -3695,10 +3751,18 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
   return 0;
 }
 
+int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int32_t n_assigned, const int32_t *pdb_allowed,
+                               int32_t n_pdb) {
+  return koordhip_preempt_load_pods_ext(c, a, nullptr, n_assigned, pdb_allowed, n_pdb);
+}
+
 int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
-  if (flags & ~(KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV))
+  if (flags & ~(KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE))
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: unknown flag bit");
+  // a profile without DeviceShare can never hold the DEVICE mode's state: the bit is refused like an unknown one
+  if ((flags & KOORDHIP_PREEMPT_DEVICE) && !((c->cfg.filter_plugins | c->cfg.score_plugins) & KOORDHIP_PLUGIN_DEVICESHARE))
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: KOORDHIP_PREEMPT_DEVICE on a profile without DeviceShare");
   // Where NodeNUMAResource is in the Filter the word decides what the dry-run calls accept, so a bit the profile
   // has no plugin for is refused like an unknown one (a host that sets KOORDHIP_PREEMPT_RESV there expects
   // Reservation state the context can never hold).  On a profile without that plugin both bits are inert.
@@ -3719,12 +3783,19 @@ struct PreemptInputs {
   const kh::DevPre *dp;
   const uint64_t *plane;
   kh::WalkMode mode;
+  kh::DevWalk dw;  // the DEVICE mode's second table and the uploaded koordhip_pod_ext records
 };
 static int preempt_inputs(koordhip_ctx *c, int32_t n_pre, PreemptInputs *in) {
   in->tab = static_cast<const kh::DevAsg *>(c->d_pre_tab);
   in->off = kh::preempt_off(static_cast<int32_t *>(c->d_pre_ws), c->n);
   in->dp = static_cast<const kh::DevPre *>(c->d_pre_in);
   in->mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
+  in->dw = kh::DevWalk{};
+  if (in->mode.dev) {
+    in->mode.dev = c->pre_any_device ? 2 : 1;  // per launch: the devices move only for a call with a device preemptor
+    in->dw.xtab = c->pre_has_x ? static_cast<const kh::DevAsgX *>(c->d_pre_xtab) : nullptr;
+    in->dw.px = c->d_pre_px;
+  }
   in->plane = nullptr;
   if (!in->mode.numa || n_pre <= 0 || c->n <= 0) return 0;
   if (int e = ensure(c, &c->d_pre_plane, &c->pre_plane_cap, kh::preempt_plane_words(c->n, n_pre) * sizeof(uint64_t)))
@@ -3762,7 +3833,7 @@ static int preempt_carve(koordhip_ctx *c, void **buf, size_t *cap, size_t align,
 // The checks the dry-run calls share, and the preemptors' upload (out: where the call's answer goes; stream:
 // koordhip_preempt_stream asks).
 static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, const void *out,
-                         int32_t max_victims, bool stream) {
+                         int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr) {
   if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
   const kh::WalkMode mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
@@ -3770,9 +3841,49 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (!c->pre_loaded)
     return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
                                  "load_snapshot)");
-  if (c->seq || c->seq_profile)
+  if (mode.dev) {
+    // the DEVICE mode: DeviceShare (and the normalized static Scores, which no dry run reads) and nothing else of
+    // the sequential cycle
+    if (stream)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "
+                                   "KOORDHIP_PREEMPT_DEVICE (gone victims' devices and extended scalars would have "
+                                   "to leave the call-scoped overlay)");
+    if ((c->cfg.filter_plugins | c->cfg.score_plugins) & (KOORDHIP_PLUGIN_PTS | KOORDHIP_PLUGIN_IPA))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE not with PodTopologySpread or "
+                                   "InterPodAffinity in the profile (they keep AddPod / RemovePod state of their own)");
+    if (mode.resv || c->d.dv.rslot || c->d.dv.rxa)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE not with Reservation state (the plugin in "
+                                   "the profile, reservation or resv_dev_slot columns), with or without "
+                                   "KOORDHIP_PREEMPT_RESV: that combination (preemptibleInRRs, "
+                                   "tryAllocateFromReservation) is the follow-up, not built");
+  } else if (c->seq || c->seq_profile) {
+    if (stream && mode.devp)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "
+                                   "KOORDHIP_PREEMPT_DEVICE (gone victims' devices and extended scalars would have "
+                                   "to leave the call-scoped overlay)");
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: the profile / snapshot evaluates in the sequential cycle "
-                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered");
+                                 "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered; "
+                                 "a profile whose sequential-cycle plugins are DeviceShare only is accepted after "
+                                 "koordhip_preempt_set_mode(KOORDHIP_PREEMPT_DEVICE)");
+  }
+  if (ext && !mode.dev)
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_ext: koordhip_pod_ext records outside the KOORDHIP_PREEMPT_DEVICE mode");
+  bool any_device = false;
+  if (ext) {
+    bool any = false;
+    if (int e = check_pod_ext(ext, n_pre, &any)) return e;
+    for (int32_t p = 0; p < n_pre; p++) {
+      const koordhip_pod_ext &x = ext[p];
+      if (x.pts_n || x.pts_match || x.pts_class || (x.ipa_inc | x.ipa_aff | x.ipa_anti | x.ipa_score | x.ipa_flags) ||
+          x.reserve_node)
+        return fail(KOORDHIP_EINVAL, "koordhip_preempt_ext: a koordhip_pod_ext record with spread, affinity or reserve "
+                                     "fields set (only dev_req, xreq, xmask and KOORDHIP_PODX_DEVICE are read)");
+      for (int k = 0; k < KOORDHIP_NXRES; k++)
+        if (((x.xmask >> k) & 1u) && (x.xreq[k] < 0 || x.xreq[k] >= kDevQtyLimit))
+          return fail(KOORDHIP_EINVAL, "koordhip_preempt_ext: xreq outside [0, 2^45)");
+      any_device = any_device || (x.flags & KOORDHIP_PODX_DEVICE);
+    }
+  }
   if ((c->dc.filt & KOORDHIP_PLUGIN_NUMA) && !mode.numa)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with NodeNUMAResource in the Filter (it has no "
                                  "PreFilterExtensions: its state does not move in a dry run) unless "
@@ -3825,15 +3936,24 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   const size_t pb = (size_t)n_pre * sizeof(kh::DevPre);
   if (int e = ensure(c, &c->d_pre_in, &c->pre_in_cap, pb)) return e;
   HIP_TRY(hipMemcpyAsync(c->d_pre_in, dp.data(), pb, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));  // dp is this function's
+  std::vector<koordhip_pod_ext> none;
+  if (mode.dev && n_pre > 0) {  // the preemptors' ext records (NULL: all empty)
+    const size_t xb = (size_t)n_pre * sizeof(koordhip_pod_ext);
+    static_assert(sizeof(kh::DevPodX) == sizeof(koordhip_pod_ext), "uploaded as they are");
+    if (int e = ensure(c, &c->d_pre_px, &c->pre_px_cap, xb)) return e;
+    if (!ext) none.assign((size_t)n_pre, koordhip_pod_ext{});
+    HIP_TRY(hipMemcpyAsync(c->d_pre_px, ext ? ext : none.data(), xb, hipMemcpyHostToDevice, c->stream));
+  }
+  c->pre_any_device = any_device;
+  HIP_TRY(hipStreamSynchronize(c->stream));  // dp and none are this function's
   return 0;
 }
 
 // The entry of koordhip_preempt and koordhip_preempt_stream: preempt_ready, then the answer that needs no
 // launch.  With no preemptor or no node the caller returns; without a node nobody has a pick or a victim.
 static int preempt_enter(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
-                         int32_t *victims, int32_t max_victims, bool stream) {
-  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream)) return e;
+                         int32_t *victims, int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr) {
+  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream, ext)) return e;
   if (n_pre == 0 || c->n > 0) return 0;
   std::memset(out, 0, (size_t)n_pre * sizeof(*out));
   for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
@@ -3841,9 +3961,9 @@ static int preempt_enter(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   return 0;
 }
 
-int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
-                     int32_t *victims, int32_t max_victims) {
-  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, false)) return e;
+int koordhip_preempt_ext(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext, int32_t n_pre,
+                         koordhip_preempt_result *out, int32_t *victims, int32_t max_victims) {
+  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, false, ext)) return e;
   if (n_pre == 0 || c->n == 0) return 0;
   const size_t nb = (size_t)kh::preempt_blocks(c->n);
   const size_t nv = victims ? (size_t)n_pre * max_victims : 0;
@@ -3863,13 +3983,18 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
   HIP_TRY(hipMemsetAsync(d_cnt, 0, (char *)d_part - (char *)d_cnt, c->stream));  // the counts, rounded up
   if (nv) HIP_TRY(hipMemsetAsync(d_vic, 0xFF, vb, c->stream));
   HIP_TRY(kh::launch_preempt(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, d_cnt, d_part, nullptr, in.plane,
-                             in.mode, c->stream));
+                             in.mode, c->stream, in.dw));
   HIP_TRY(kh::launch_preempt_pick(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, d_cnt, d_part, d_res, d_vic,
-                                  max_victims, in.mode, c->stream));
+                                  max_victims, in.mode, c->stream, in.dw));
   HIP_TRY(hipMemcpyAsync(out, d_res, rb, hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, d_vic, vb, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                     int32_t *victims, int32_t max_victims) {
+  return koordhip_preempt_ext(c, pre, nullptr, n_pre, out, victims, max_victims);
 }
 
 // The sequential dry run: every buffer that changes during the call is carved
@@ -3923,8 +4048,9 @@ int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int3
   return 0;
 }
 
-int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pre, koordhip_preempt_node *per_node) {
-  if (int e = preempt_ready(c, pre, 1, per_node, 0, false)) return e;
+int koordhip_preempt_node_verdicts_ext(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext,
+                                       koordhip_preempt_node *per_node) {
+  if (int e = preempt_ready(c, pre, 1, per_node, 0, false, ext)) return e;
   const int32_t n = c->n;
   if (n == 0) return 0;
   int32_t *d_cnt;
@@ -3940,10 +4066,14 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pr
   if (int e = preempt_inputs(c, 1, &in)) return e;
   HIP_TRY(hipMemsetAsync(d_cnt, 0, 8 * sizeof(int32_t), c->stream));
   HIP_TRY(kh::launch_preempt(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, 1, d_cnt, d_part, d_ver, in.plane, in.mode,
-                             c->stream));
+                             c->stream, in.dw));
   HIP_TRY(hipMemcpyAsync(per_node, d_ver, (size_t)n * sizeof(*per_node), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+int koordhip_preempt_node_verdicts(koordhip_ctx *c, const koordhip_preemptor *pre, koordhip_preempt_node *per_node) {
+  return koordhip_preempt_node_verdicts_ext(c, pre, nullptr, per_node);
 }
 
 int koordhip_last_stats(koordhip_ctx *c, double *eval_ms, int64_t *eval_launches, int64_t *evals, double *total_ms) {

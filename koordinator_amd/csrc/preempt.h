@@ -18,6 +18,21 @@ struct DevAsg {
   int32_t node;
 };
 static_assert(sizeof(DevAsg) == 160 && sizeof(DevAsg) % 16 == 0, "DevAsg is 160 bytes");
+// DevAsg::flags bit the library sets (a caller's bit there is dropped): the pod's record of the second table
+// (DevAsgX) is not empty.  A walk reads that table for such records only.
+constexpr uint32_t ASG_HAS_EXT = 4u;
+
+// Device copy of one koordhip_assigned_ext (same layout): what a listed pod holds of the extended scalars and
+// of its node's devices.  The second table is permuted with the first, so list[k]'s record is xlist[k].
+struct DevAsgX {
+  int64_t xreq[KOORDHIP_NXRES];
+  int64_t dev_per[KOORDHIP_DEV_TYPES][KOORDHIP_DEV_RES];
+  uint32_t dev_slots[KOORDHIP_DEV_TYPES];
+  uint32_t xmask;
+  uint64_t reserved;
+};
+static_assert(sizeof(DevAsgX) == sizeof(koordhip_assigned_ext) && sizeof(DevAsgX) == sizeof(DevAsg),
+              "DevAsgX mirrors koordhip_assigned_ext and permutes like DevAsg");
 
 // Device copy of one koordhip_preemptor.
 struct DevPre {
@@ -49,7 +64,16 @@ inline int32_t preempt_blocks(int32_t n) { return (n + PREEMPT_THREADS - 1) / PR
 //   ws  int32 workspace of preempt_ws_ints(n, m) words: cnt [n + 1], off [n + 1], nl [m], tot [1]
 size_t preempt_ws_ints(int32_t n, int32_t m);
 inline int32_t *preempt_off(int32_t *ws, int32_t n) { return ws + n + 1; }
-hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s);
+// xraw / xsorted: the second table (DevAsgX, NULL: none), permuted by the same order.
+hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s,
+                                const void *xraw = nullptr, void *xsorted = nullptr);
+
+// The DEVICE mode's inputs of a dry-run call (m.dev > 0; empty otherwise): the permuted second table (NULL: no
+// listed pod holds a scalar or a device) and the preemptors' koordhip_pod_ext records.
+struct DevWalk {
+  const DevAsgX *xtab;
+  const void *px;  // DevPodX [n_pre] (dev.hpp)
+};
 
 // Which walk a dry-run call runs: what the profile / snapshot holds and what
 // koordhip_preempt_set_mode's flags accepted of it.  The launchers pick their
@@ -59,12 +83,17 @@ struct WalkMode {
   bool resv;  // the context has Reservation state (the Filter plugin or reservation columns) ...
   int rs;     // ... and the host accepted the walk that keeps the plugin's AddPod / RemovePod state: the
               // reservation slots per row (1, or KOORDHIP_RESV_SLOTS where the snapshot's resv_slots ask), else 0
+  bool devp;  // DeviceShare is in the profile (Filter or Score) ...
+  int dev;    // ... and the host accepted the walk that moves the victims' extended scalars (1) and, for a call
+              // with a device preemptor, their devices (2: the launchers' callers raise 1 to 2 per call); else 0
 };
 inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
   WalkMode m{};
   m.numa = (pre_mode & KOORDHIP_PREEMPT_NUMA_FROZEN) && (c.filt & KOORDHIP_PLUGIN_NUMA);
   m.resv = c.resv || (c.filt & KOORDHIP_PLUGIN_RESERVATION);
   m.rs = (pre_mode & KOORDHIP_PREEMPT_RESV) && m.resv ? (c.resv_slots > 1 ? KOORDHIP_RESV_SLOTS : 1) : 0;
+  m.devp = ((c.filt | c.score) & KOORDHIP_PLUGIN_DEVICESHARE) != 0;
+  m.dev = (pre_mode & KOORDHIP_PREEMPT_DEVICE) && m.devp ? 1 : 0;
   return m;
 }
 
@@ -77,11 +106,12 @@ inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
 // plugin's verdict there and evaluates filterAmplifiedCPUs on every row), else
 // NULL.  With m.rs the walk starts from the restored row and keeps the plugin's
 // AddPod / RemovePod state; DevAsg::flags bits 8-11 name the slot a listed pod
-// is bound to.
+// is bound to.  With m.dev (rs 0 only) the walk moves the listed pods'
+// extended scalars (1) and devices (2) as dw describes them.
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
                           PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, WalkMode m,
-                          hipStream_t s);
+                          hipStream_t s, DevWalk dw = DevWalk{});
 // The frozen NUMA verdict plane of pre[0, n_pre): plane [n_pre][2][ceil(n / 64)]
 // u64 (preempt_plane_words), bit b of word w is node 64 w + b; [p][0]: the
 // NodeNUMAResource Filter without filterAmplifiedCPUs fails on the loaded NUMA
@@ -94,7 +124,7 @@ hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre 
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, WalkMode m, hipStream_t s);
+                               int32_t max_victims, WalkMode m, hipStream_t s, DevWalk dw = DevWalk{});
 
 // ---- the sequential dry run (koordhip_preempt_stream) ----------------------
 // Preemptor k is answered on the state the preemptors before it left: their

@@ -47,6 +47,10 @@
 // the plugin's AddPod / RemovePod state (preemptible, preemptibleInRRs:
 // resv.hpp ResvPre) per (preemptor, node) in registers; RS = 1 or
 // KOORDHIP_RESV_SLOTS reservation slots per node.  Not in the stream.
+// DEV > 0 (KOORDHIP_PREEMPT_DEVICE, with RS = 0 and not in the stream): the
+// listed pods' extended scalars move with them (1), and for a call with a
+// device preemptor so do their devices (2): DeviceShare's preemptibleDevices
+// per (preemptor, node) as used - Pd in LDS, one column per thread.
 //
 // Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
 // reads the row the previous add / remove left), so a wave would hold 63 idle
@@ -57,6 +61,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "dev.hpp"
 #include "diag.h"
 #include "eval.hpp"
 #include "preempt.h"
@@ -191,6 +196,63 @@ using WalkRow = NumaRowRS<(RS > 0 ? RS : 1)>;
 // the reservation slot of its node a listed pod is bound to, -1: none
 __device__ __forceinline__ int asg_slot(const DevAsg &a) { return (int)((a.flags >> 8) & 15u) - 1; }
 
+// What the DEVICE mode adds to one (preemptor, node): the node's device columns, the list's second table, P's
+// koordhip_pod_ext record and the thread's column of the walk's device state (DEV = 2): u[((t * DS + s) * DR
+// + r) * stride] is used - Pd of slot s of type t, kept for the types P requests.
+struct DevSide {
+  const DevDev *dv;
+  const DevAsgX *xlist;
+  const DevPodX *x;
+  int64_t *u;
+  int32_t stride;
+  int32_t i, n;
+};
+
+__device__ __forceinline__ int64_t &dev_u(const DevSide &ds, int t, int s, int r) {
+  return ds.u[(size_t)((t * DS + s) * DR + r) * ds.stride];
+}
+
+// The DeviceShare Filter of a device preemptor on a nodeDevice node with the walk's preemptible devices
+// (plugin.go:284-323 with preemptible, device_cache.go:316-365): dev_eval's rule with the free amounts of a
+// slot taken as max0(total - max0(used - Pd)) (calcFreeWithPreemptible, :454-482; with Pd = 0 that is
+// deviceFree, so the one formula serves the minors the map does not list).  tm: the types P requests.
+__device__ __forceinline__ bool dev_filter_pre(const DevSide &ds, uint32_t tm) {
+  const DevDev &dv = *ds.dv;
+  bool ok = true;
+#pragma unroll 1
+  for (int t = 0; t < DT; t++) {
+    if (!((tm >> t) & 1u)) continue;
+    int64_t q[DR];
+    dev_requests(*ds.x, t, q);
+    DevRow w;
+    const size_t a0 = dev_at(dv, ds.i, t, 0);
+#pragma unroll
+    for (int s = 0; s < DS; s++) {
+      const bool on = s < dv.slots;
+      w.minor[s] = on ? dv.minor[a0 + s] : -1;
+#pragma unroll
+      for (int r = 0; r < DR; r++) {
+        const int64_t tt = on ? dv.total[(a0 + s) * DR + r] : 0;
+        const int64_t uu = on ? dev_u(ds, t, s, r) : 0;
+        const int64_t f = tt - (uu > 0 ? uu : 0);
+        w.tot[s][r] = tt;
+        w.fr[s][r] = f > 0 ? f : 0;
+      }
+    }
+    if (!dev_has_type(w) || (t == KOORDHIP_DEV_GPU && !dev_fill_gpu(w, q))) {
+      ok = false;
+      continue;
+    }
+    int64_t per[DR];
+    const int64_t want = dev_wanted(t, q, per);
+    int64_t cnt = 0;
+#pragma unroll
+    for (int s = 0; s < DS; s++) cnt += (w.minor[s] >= 0 && !dev_zero(w.fr[s]) && dev_fits(per, w.fr[s])) ? 1 : 0;
+    ok &= cnt >= want;
+  }
+  return ok;
+}
+
 // some pod of the list is a potential victim of P
 template <bool OVL>
 __device__ __forceinline__ bool any_potential(const DevAsg *__restrict__ list, int32_t len, const NodeOverlay &ov,
@@ -206,15 +268,45 @@ __device__ __forceinline__ bool any_potential(const DevAsg *__restrict__ list, i
   return any;
 }
 
-template <int EMIT, bool OVL, bool NUMA, int RS = 0>
+//
+// DEV > 0 (KOORDHIP_PREEMPT_DEVICE; ds): NodeResourcesFit also tests P's extended scalars on xrequested, which
+// moves with every listed pod that holds some (its DevAsgX record, read for ASG_HAS_EXT records only).  DEV = 2:
+// and for a device preemptor on a nodeDevice node every move of a listed pod moves the devices it holds into /
+// out of preemptibleDevices, which the DeviceShare Filter of every fit test frees (dev_filter_pre).
+template <int EMIT, bool OVL, bool NUMA, int RS = 0, int DEV = 0>
 __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
                                                               const WalkRow<RS> &nr, const DevAsg *__restrict__ list,
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
                                                               int32_t *vout, int32_t vmax, const NodeOverlay &ov,
-                                                              uint32_t fcode) {
+                                                              uint32_t fcode, const DevSide &ds = DevSide{}) {
   static_assert(!(OVL && RS > 0), "the sequential dry run holds no Reservation state");
+  static_assert(DEV == 0 || (!OVL && RS == 0), "the DEVICE mode: not in the stream, not with Reservation state");
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
+  // xfree[j] = Allocatable - Requested of extended scalar j, for P's scalars (DEV > 0); tm: the device types of P
+  // whose preemptible state the walk keeps (DEV = 2; 0: DeviceShare passes whatever is removed)
+  int64_t xfree[KOORDHIP_NXRES] = {};
+  uint32_t xm = 0u, tm = 0u;
+  if constexpr (DEV > 0) {
+    xm = (c.filt & KOORDHIP_PLUGIN_FIT) ? ds.x->xmask : 0u;
+#pragma unroll
+    for (int j = 0; j < KOORDHIP_NXRES; j++)
+      if ((xm >> j) & 1u)
+        xfree[j] = (ds.dv->xalloc ? ds.dv->xalloc[(size_t)j * ds.n + ds.i] : 0) - ds.dv->xreq[(size_t)j * ds.n + ds.i];
+  }
+  auto xfit_ok = [&]() {
+    bool ok = true;
+    if constexpr (DEV > 0) {
+#pragma unroll
+      for (int j = 0; j < KOORDHIP_NXRES; j++)
+        if ((xm >> j) & 1u) ok &= ds.x->xreq[j] <= xfree[j];
+    }
+    return ok;
+  };
+  auto dev_ok = [&]() {
+    if constexpr (DEV == 2) return tm == 0u || dev_filter_pre(ds, tm);
+    return true;
+  };
   auto amp_ok = [&](const NV &x) {
     if constexpr (NUMA) return !c.amp || amp_filter_ok(pod, x, nr);
     return true;
@@ -261,7 +353,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   if constexpr (NUMA) {
     if (fcode) {
       // the first failing plugin in Filter order decides whether preemption might help
-      if ((fcode & NUMA_F_UNRESOLVABLE) && base_status(w) == 0u && amp_ok(w)) {
+      if ((fcode & NUMA_F_UNRESOLVABLE) && base_status(w) == 0u && xfit_ok() && amp_ok(w)) {
         r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
         return r;
       }
@@ -281,9 +373,47 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       return r;
     }
   }
-  auto move = [&](QuotaUsed &qu, const DevAsg &a, int sign) {
+  if constexpr (DEV == 2) {
+    // the state of the types P requests: used - Pd with Pd empty
+    const DevDev &dv = *ds.dv;
+    if ((c.filt & KOORDHIP_PLUGIN_DEVICESHARE) && (ds.x->flags & KOORDHIP_PODX_DEVICE) && dev_present(dv, ds.i)) {
+#pragma unroll
+      for (int t = 0; t < DT; t++) {
+        int64_t q[DR];
+        if (!dev_requests(*ds.x, t, q)) continue;
+        tm |= 1u << t;
+        const size_t a0 = dev_at(dv, ds.i, t, 0) * DR;
+#pragma unroll
+        for (int s = 0; s < DS; s++)
+#pragma unroll
+          for (int rr = 0; rr < DR; rr++) dev_u(ds, t, s, rr) = s < dv.slots ? dv.used[a0 + (size_t)s * DR + rr] : 0;
+      }
+    }
+  }
+  // list[k] leaves (-1) or rejoins (+1)
+  auto move = [&](QuotaUsed &qu, const DevAsg &a, int32_t k, int sign) {
     move_pod(w, qu, a, sign);
     if constexpr (RS > 0) resv_pre_move(rp, a.pod, asg_slot(a), sign);
+    if constexpr (DEV > 0) {
+      if ((a.flags & ASG_HAS_EXT) && (xm | tm)) {
+        const DevAsgX &ax = ds.xlist[k];
+#pragma unroll
+        for (int j = 0; j < KOORDHIP_NXRES; j++)
+          if ((xm >> j) & 1u) xfree[j] -= sign * ax.xreq[j];
+        if constexpr (DEV == 2) {
+#pragma unroll
+          for (int t = 0; t < DT; t++) {
+            const uint32_t sl = ((tm >> t) & 1u) ? ax.dev_slots[t] : 0u;
+            if (!sl) continue;
+#pragma unroll
+            for (int s = 0; s < DS; s++)
+              if ((sl >> s) & 1u)
+#pragma unroll
+                for (int rr = 0; rr < DR; rr++) dev_u(ds, t, s, rr) += sign * ax.dev_per[t][rr];
+          }
+        }
+      }
+    }
   };
   QuotaUsed q;
   int32_t pa[KOORDHIP_PREEMPT_PDBS];
@@ -299,7 +429,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     }
     const DevAsg &a = list[k];
     if ((a.flags & KOORDHIP_ASG_NONPREEMPTIBLE) || a.prio >= pprio || a.quota != pquota) continue;
-    move(q, a, -1);
+    move(q, a, k, -1);
     const uint32_t pm = a.pdb_mask;
     bool bad = false;
 #pragma unroll
@@ -321,7 +451,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     r.status = KOORDHIP_PREEMPT_NO_VICTIMS;
     return r;
   }
-  if (base_status(w) != 0u || !amp_ok(w) || !resv_ok(w)) {
+  if (base_status(w) != 0u || !xfit_ok() || !amp_ok(w) || !resv_ok(w) || !dev_ok()) {
     r.status = KOORDHIP_PREEMPT_UNFIT;
     return r;
   }
@@ -337,9 +467,9 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       const int32_t k = (int32_t)__ffsll((unsigned long long)m) - 1 + ((g & 1) ? 64 : 0);
       m &= m - 1;
       const DevAsg &a = list[k];
-      move(q, a, +1);
-      const bool fits = base_status(w) == 0u && amp_ok(w) && resv_ok(w);
-      if (!fits) move(q, a, -1);
+      move(q, a, k, +1);
+      const bool fits = base_status(w) == 0u && xfit_ok() && amp_ok(w) && resv_ok(w) && dev_ok();
+      if (!fits) move(q, a, k, -1);
       bool over = false;
       if (pquota >= 0) {
 #pragma unroll
@@ -352,7 +482,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         return e;
       }
       if (fits && !over) continue;  // reprieved
-      if (over) move(q, a, -1);
+      if (over) move(q, a, k, -1);
       if (!fits && violating) npdb++;
       const int32_t ap = a.prio;
       const int64_t as = a.start;
@@ -389,10 +519,11 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
 // the same masks (the NodeNUMAResource Filter arrives as preempt_node's fcode),
 // with amp kept for filterAmplifiedCPUs.  RS > 0: the Reservation Filter bit
 // and resv stay (the restore and the walk's own filterWithReservations).
-template <bool NUMA, int RS = 0>
+// DEV > 0: and the DeviceShare Filter bit (the walk's own xfit / dev_filter_pre read it).
+template <bool NUMA, int RS = 0, int DEV = 0>
 __device__ __forceinline__ DevCfg envelope(DevCfg c) {
   c.filt &= KOORDHIP_PLUGIN_FIT | KOORDHIP_PLUGIN_LOADAWARE | KOORDHIP_PLUGIN_NODE_STATIC |
-            (RS > 0 ? KOORDHIP_PLUGIN_RESERVATION : 0u);
+            (RS > 0 ? KOORDHIP_PLUGIN_RESERVATION : 0u) | (DEV > 0 ? KOORDHIP_PLUGIN_DEVICESHARE : 0u);
   c.score = 0;
   if constexpr (RS == 0) c.resv = 0;
   c.zones = 0;
@@ -443,13 +574,14 @@ struct WalkNode {
   WalkRow<RS> nr{};
   const DevAsg *list;
   int32_t len;
+  const DevAsgX *xlist;  // the list's records of the second table (the DEVICE mode; NULL: none)
 };
 
 // Node i under the envelope c.  live = false: a tail lane, which reads the last row and walks an empty list.
 template <bool NUMA, int RS>
 __device__ __forceinline__ WalkNode<RS> load_walk_node(const DevCfg &c, const DevNodes &d,
                                                        const DevAsg *__restrict__ tab, const int32_t *__restrict__ off,
-                                                       int32_t i, bool live = true) {
+                                                       int32_t i, bool live = true, const DevAsgX *xtab = nullptr) {
   const int32_t il = live ? i : d.n - 1;
   WalkNode<RS> x;
   const Need all = need_all(c);
@@ -458,6 +590,7 @@ __device__ __forceinline__ WalkNode<RS> load_walk_node(const DevCfg &c, const De
   const int32_t lo = off[il];
   x.len = live ? min(off[il + 1] - lo, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
   x.list = tab + lo;
+  x.xlist = xtab ? xtab + lo : nullptr;
   return x;
 }
 
@@ -468,6 +601,34 @@ __device__ __forceinline__ const DevPre *stage_pre(const DevPre *__restrict__ pr
   const uint64_t *src = reinterpret_cast<const uint64_t *>(pre + p0);
   for (int32_t w = threadIdx.x; w < np * PRE_WORDS; w += PREEMPT_THREADS) spw[w] = src[w];
   return reinterpret_cast<const DevPre *>(spw);
+}
+
+// The DEV = 2 walk's device state of a workgroup of THREADS threads: DT x DS x DR int64 per thread do not fit the
+// register file beside the row, so they live in LDS, [t][s][r][thread]: a thread's words are its own (no
+// barrier), a wave's 64 consecutive words of one (t, s, r) go to distinct banks.  At 256 threads that is 144 KB:
+// one workgroup per CU, one wave per SIMD, which is what the walk's 200+ registers allow anyway.
+template <int DEV, int THREADS>
+__device__ __forceinline__ int64_t *dev_state() {
+  if constexpr (DEV == 2) {
+    __shared__ __attribute__((aligned(16))) int64_t su[DT * DS * DR * THREADS];
+    return su + threadIdx.x;
+  } else {
+    return nullptr;
+  }
+}
+
+template <int THREADS>
+__device__ __forceinline__ DevSide dev_side(const DevNodes &d, const DevAsgX *xlist, const DevPodX *x, int64_t *u,
+                                            int32_t i) {
+  DevSide ds;
+  ds.dv = &d.dv;
+  ds.xlist = xlist;
+  ds.x = x;
+  ds.u = u;
+  ds.stride = THREADS;
+  ds.i = i;
+  ds.n = d.n;
+  return ds;
 }
 
 // ---------------------------------------------------------------------------
@@ -581,15 +742,17 @@ __device__ __forceinline__ koordhip_preempt_result pick_result(const koordhip_pr
 
 // BLK: the workgroup's counts go to bcnt [n_pre][gridDim.x][5] instead of
 // being summed into count (the sequential dry run replaces single blocks).
-// NUMA: pl holds the frozen verdicts of pre[0, n_pre).  RS: preempt_node's.
-template <bool BLK, bool NUMA, int RS = 0>
+// NUMA: pl holds the frozen verdicts of pre[0, n_pre).  RS, DEV: preempt_node's (dw: the DEVICE mode's inputs).
+template <bool BLK, bool NUMA, int RS = 0, int DEV = 0>
 __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes &d, const DevAsg *__restrict__ tab,
                                               const int32_t *__restrict__ off, const PdbAllowed &pdb,
                                               const DevPre *__restrict__ pre, int32_t n_pre,
                                               int32_t *__restrict__ count, PreemptPartial *__restrict__ part,
                                               koordhip_preempt_node *__restrict__ per_node,
-                                              int32_t *__restrict__ bcnt, const NumaPlane &pl) {
-  const DevCfg c = envelope<NUMA, RS>(cfg);
+                                              int32_t *__restrict__ bcnt, const NumaPlane &pl,
+                                              const DevWalk &dw = DevWalk{}) {
+  const DevCfg c = envelope<NUMA, RS, DEV>(cfg);
+  int64_t *su = dev_state<DEV, PREEMPT_THREADS>();
   __shared__ int32_t scnt[PRE_PT * KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_PT][PRE_WAVES];
   const int t = threadIdx.x, wave = t >> 6;
@@ -600,14 +763,20 @@ __device__ __forceinline__ void preempt_tiles(const DevCfg &cfg, const DevNodes 
   __syncthreads();
   const int32_t i = (int32_t)blockIdx.x * PREEMPT_THREADS + t;
   const bool live = i < d.n;
-  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i, live);
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i, live, DEV > 0 ? dw.xtab : nullptr);
   for (int32_t q = 0; q < np; q++) {
     koordhip_preempt_node r{};
     uint32_t fcode = 0u;
     if constexpr (NUMA) fcode = plane_code(pl, p0 + q, i);
-    if (live)
-      r = preempt_node<EMIT_NONE, false, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, sp[q], nullptr, 0,
-                                                    NodeOverlay{}, fcode);
+    if (live) {
+      if constexpr (DEV > 0)
+        r = preempt_node<EMIT_NONE, false, NUMA, RS, DEV>(
+            c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, sp[q], nullptr, 0, NodeOverlay{}, fcode,
+            dev_side<PREEMPT_THREADS>(d, nd.xlist, static_cast<const DevPodX *>(dw.px) + p0 + q, su, i));
+      else
+        r = preempt_node<EMIT_NONE, false, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, sp[q], nullptr, 0,
+                                                      NodeOverlay{}, fcode);
+    }
     if (per_node && live) per_node[(size_t)q * d.n + i] = r;
     wave_vote(r, i, live, &scnt[q * KOORDHIP_PREEMPT_STATUSES], &sbest[q][wave]);
   }
@@ -634,6 +803,19 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt(DevCfg cfg, DevNode
                                                              koordhip_preempt_node *__restrict__ per_node,
                                                              NumaPlane pl) {
   preempt_tiles<false, NUMA, RS>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl);
+}
+
+// ... in the DEVICE mode (DEV = 1: no device preemptor in the call, 2: some)
+template <bool NUMA, int DEV>
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_dev(DevCfg cfg, DevNodes d,
+                                                                 const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                                 const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                 int32_t *__restrict__ count,
+                                                                 PreemptPartial *__restrict__ part,
+                                                                 koordhip_preempt_node *__restrict__ per_node,
+                                                                 NumaPlane pl, DevWalk dw) {
+  preempt_tiles<false, NUMA, 0, DEV>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl, dw);
 }
 
 // Phase 1 of the sequential dry run: one tile of preemptors on the loaded
@@ -684,6 +866,26 @@ __global__ __launch_bounds__(64) void k_preempt_victims(DevCfg cfg, DevNodes d, 
   const DevPre P = pre[p];
   (void)preempt_node<EMIT_IDX, false, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P,
                                                 vout + (size_t)p * vmax, vmax, NodeOverlay{}, 0u);
+}
+
+// ... in the DEVICE mode: the chosen node again with the same function
+template <bool NUMA, int DEV>
+__global__ __launch_bounds__(64) void k_preempt_victims_dev(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                            const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                            const DevPre *__restrict__ pre, int32_t n_pre,
+                                                            const koordhip_preempt_result *__restrict__ res,
+                                                            int32_t *__restrict__ vout, int32_t vmax, DevWalk dw) {
+  const DevCfg c = envelope<NUMA, 0, DEV>(cfg);
+  int64_t *su = dev_state<DEV, 64>();
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n_pre) return;
+  const int32_t i = res[p].node;
+  if (i < 0 || i >= d.n) return;
+  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, true, dw.xtab);
+  const DevPre P = pre[p];
+  (void)preempt_node<EMIT_IDX, false, NUMA, 0, DEV>(
+      c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, vout + (size_t)p * vmax, vmax, NodeOverlay{}, 0u,
+      dev_side<64>(d, nd.xlist, static_cast<const DevPodX *>(dw.px) + p, su, i));
 }
 
 // ---------------------------------------------------------------------------
@@ -859,7 +1061,8 @@ __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, co
 
 size_t preempt_ws_ints(int32_t n, int32_t m) { return 2 * ((size_t)n + 1) + (size_t)std::max(m, 0) + 1; }
 
-hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s) {
+hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, int32_t n, int32_t *ws, hipStream_t s,
+                                const void *xraw, void *xsorted) {
   int32_t *cnt = ws, *off = preempt_off(ws, n), *nl = off + n + 1, *tot = nl + std::max(m, 0);
   hipError_t e = hipMemsetAsync(cnt, 0, ((size_t)n + 1) * sizeof(int32_t), s);
   if (e != hipSuccess) return e;
@@ -874,6 +1077,9 @@ hipError_t launch_preempt_lists(const DevAsg *raw, DevAsg *sorted, int32_t m, in
   if (n > 0) hipLaunchKernelGGL(k_pre_sort, dim3((n + 255) / 256), blk, 0, s, raw, off, nl, n);
   const int64_t words = (int64_t)m * ASG_VEC;
   hipLaunchKernelGGL(k_pre_permute, dim3((unsigned)((words + 255) / 256)), blk, 0, s, raw, sorted, nl, m);
+  if (xraw && xsorted)  // the second table by the same order: its records are DevAsg's size, copied as 16-B words
+    hipLaunchKernelGGL(k_pre_permute, dim3((unsigned)((words + 255) / 256)), blk, 0, s,
+                       static_cast<const DevAsg *>(xraw), static_cast<DevAsg *>(xsorted), nl, m);
   return hipGetLastError();
 }
 
@@ -881,8 +1087,11 @@ size_t preempt_plane_words(int32_t n, int32_t n_pre) { return (size_t)std::max(n
 
 // The launchers' argument check: m is the walk of every state the profile has (the mode with every flag
 // accepted: NodeNUMAResource in the Filter needs the plane, Reservation state the walk with its slots).
-static bool preempt_profile_ok(const DevCfg &c, WalkMode m, const uint64_t *plane) {
-  const WalkMode all = preempt_walk_mode(c, KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV);
+static bool preempt_profile_ok(const DevCfg &c, WalkMode m, const uint64_t *plane, const DevWalk &dw) {
+  const WalkMode all =
+      preempt_walk_mode(c, KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE);
+  if ((m.dev > 0) != (all.dev > 0) || m.dev > 2) return false;
+  if (m.dev > 0 && (m.rs != 0 || m.resv || !dw.px)) return false;  // DEVICE: no Reservation state, and P's records
   return m.numa == all.numa && m.rs == all.rs && m.numa == (plane != nullptr);
 }
 
@@ -903,6 +1112,21 @@ static void with_walk(WalkMode m, F f) {
     slots(std::false_type{});
 }
 
+// ... of the DEVICE mode: f(std::bool_constant<NUMA>, std::integral_constant<int, DEV>), DEV = m.dev in {1, 2}.
+template <class F>
+static void with_walk_dev(WalkMode m, F f) {
+  auto devs = [&](auto numa) {
+    if (m.dev > 1)
+      f(numa, std::integral_constant<int, 2>{});
+    else
+      f(numa, std::integral_constant<int, 1>{});
+  };
+  if (m.numa)
+    devs(std::true_type{});
+  else
+    devs(std::false_type{});
+}
+
 hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
                                hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
@@ -916,13 +1140,20 @@ hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre 
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
                           PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, WalkMode m,
-                          hipStream_t s) {
+                          hipStream_t s, DevWalk dw) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (!preempt_profile_ok(c, m, plane)) return hipErrorInvalidValue;
+  if (!preempt_profile_ok(c, m, plane, dw)) return hipErrorInvalidValue;
   if (per_node && n_pre != 1) return hipErrorInvalidValue;
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
   const NumaPlane pl{plane, (d.n + 63) / 64};
+  if (m.dev > 0) {
+    with_walk_dev(m, [&](auto numa, auto dev) {
+      hipLaunchKernelGGL((k_preempt_dev<decltype(numa)::value, decltype(dev)::value>), grid, dim3(PREEMPT_THREADS), 0, s,
+                         c, d, tab, off, pdb, pre, n_pre, count, part, per_node, pl, dw);
+    });
+    return hipGetLastError();
+  }
   with_walk(m, [&](auto numa, auto rs) {
     hipLaunchKernelGGL((k_preempt<decltype(numa)::value, decltype(rs)::value>), grid, dim3(PREEMPT_THREADS), 0, s, c, d,
                        tab, off, pdb, pre, n_pre, count, part, per_node, pl);
@@ -934,7 +1165,7 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                  int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (m.rs != 0 || !preempt_profile_ok(c, m, plane)) return hipErrorInvalidValue;
+  if (m.rs != 0 || m.devp || !preempt_profile_ok(c, m, plane, DevWalk{})) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
   const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
@@ -962,10 +1193,16 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
 hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const int32_t *count,
                                const PreemptPartial *part, koordhip_preempt_result *res, int32_t *victims,
-                               int32_t max_victims, WalkMode m, hipStream_t s) {
+                               int32_t max_victims, WalkMode m, hipStream_t s, DevWalk dw) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
-  if (victims && max_victims > 0)
+  if (victims && max_victims > 0 && m.dev > 0)
+    with_walk_dev(m, [&](auto numa, auto dev) {
+      hipLaunchKernelGGL((k_preempt_victims_dev<decltype(numa)::value, decltype(dev)::value>),
+                         dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims,
+                         max_victims, dw);
+    });
+  else if (victims && max_victims > 0)
     with_walk(m, [&](auto numa, auto rs) {
       hipLaunchKernelGGL((k_preempt_victims<decltype(numa)::value, decltype(rs)::value>), dim3((n_pre + 63) / 64),
                          dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims, max_victims);

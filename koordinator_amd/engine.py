@@ -358,15 +358,38 @@ class PlacementEngine:
         return out
 
     # ---- preemption dry run (koordinator_amd.preemption builds the records)
-    def preempt_load_pods(self, assigned: np.ndarray, pdb_allowed=()):
+    def preempt_load_pods(self, assigned: np.ndarray, pdb_allowed=(), ext=None):
         """Upload the table of the pods that sit on the nodes (abi.ASSIGNED_DTYPE)
-        and the PDBs' DisruptionsAllowed; valid until the next call or load_snapshot."""
+        and the PDBs' DisruptionsAllowed; valid until the next call or load_snapshot.
+        ext: abi.ASSIGNED_EXT_DTYPE records beside them (the extended scalars and
+        devices the pods hold, preemption.assigned_ext_records), read by the dry
+        run under DeviceShare (preempt_set_mode(device=True))."""
         a = np.ascontiguousarray(assigned, dtype=abi.ASSIGNED_DTYPE)
         pdb = np.ascontiguousarray(pdb_allowed, dtype=np.int32)
-        abi.check(self.lib, self.lib.koordhip_preempt_load_pods(self._ctx, a.ctypes.data, len(a),
-                                                                abi.ptr(pdb, C.c_int32), len(pdb)))
+        if ext is None:
+            abi.check(self.lib, self.lib.koordhip_preempt_load_pods(self._ctx, a.ctypes.data, len(a),
+                                                                    abi.ptr(pdb, C.c_int32), len(pdb)))
+            return
+        x = np.ascontiguousarray(ext, dtype=abi.ASSIGNED_EXT_DTYPE)
+        if len(x) != len(a):
+            raise ValueError("preempt_load_pods: one ext record per assigned pod")
+        self._need("koordhip_preempt_load_pods_ext")
+        abi.check(self.lib, self.lib.koordhip_preempt_load_pods_ext(self._ctx, a.ctypes.data, x.ctypes.data, len(a),
+                                                                    abi.ptr(pdb, C.c_int32), len(pdb)))
 
-    def preempt_set_mode(self, numa_frozen: bool = False, resv: bool = False, flags: int = None):
+    def _need(self, symbol: str):
+        if not hasattr(self.lib, symbol):
+            raise RuntimeError(f"this libkoordhip build has no {symbol}")
+
+    def _pre_ext(self, ext, n: int):
+        if ext is None:
+            return None
+        x = np.ascontiguousarray(np.atleast_1d(ext), dtype=abi.POD_EXT_DTYPE)
+        if len(x) != n:
+            raise ValueError("one koordhip_pod_ext record per preemptor")
+        return x
+
+    def preempt_set_mode(self, numa_frozen: bool = False, resv: bool = False, flags: int = None, device: bool = False):
         """numa_frozen: the dry-run calls accept NodeNUMAResource in the Filter,
         with the plugin's verdict frozen for the call: victims' cpusets and
         zone amounts are not freed and a nominated cpuset preemptor holds no
@@ -377,24 +400,40 @@ class PlacementEngine:
         preempt_stream() still refuses it.  The shipped profile needs both;
         on a profile with NodeNUMAResource in the Filter and without the
         Reservation plugin resv=True is refused (KOORDHIP_EINVAL).
+        device: preempt() and preempt_node_verdicts() accept a profile whose
+        sequential-cycle plugins are DeviceShare only: victims' extended scalars
+        and devices are freed in the walk (preempt_load_pods(ext=...), the
+        preemptors' records as preempt(ext=...)); refused on a profile without
+        DeviceShare, with PodTopologySpread / InterPodAffinity or Reservation
+        state, and by preempt_stream().
         The mode is the context's; False restores the refusal.  flags: the raw
         abi.PREEMPT_* word instead."""
         if not hasattr(self.lib, "koordhip_preempt_set_mode"):
             raise RuntimeError("this libkoordhip build has no koordhip_preempt_set_mode")
-        word = ((abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) | (abi.PREEMPT_RESV if resv else 0)) if flags is None \
-            else int(flags)
+        word = ((abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) | (abi.PREEMPT_RESV if resv else 0) |
+                (abi.PREEMPT_DEVICE if device else 0)) if flags is None else int(flags)
         abi.check(self.lib, self.lib.koordhip_preempt_set_mode(self._ctx, word))
 
-    def preempt(self, preemptors: np.ndarray, max_victims: int = 0):
+    def preempt(self, preemptors: np.ndarray, max_victims: int = 0, ext=None):
         """SelectVictimsOnNode on every node and the candidate pick, per
         preemptor (abi.PREEMPTOR_DTYPE) against the current state: returns
         (abi.PREEMPT_RESULT_DTYPE [p], victims [p][max_victims] as indices into
-        the loaded table, -1 padded).  Writes no engine state."""
+        the loaded table, -1 padded).  Writes no engine state.  ext: the
+        preemptors' abi.POD_EXT_DTYPE records (the DeviceShare mode; None: no
+        device or extended-scalar request)."""
         pre = np.ascontiguousarray(np.atleast_1d(preemptors), dtype=abi.PREEMPTOR_DTYPE)
         out = np.zeros(len(pre), abi.PREEMPT_RESULT_DTYPE)
         vic = np.full((len(pre), max_victims), -1, np.int32)
-        abi.check(self.lib, self.lib.koordhip_preempt(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
-                                                      abi.ptr(vic, C.c_int32) if max_victims else None, max_victims))
+        x = self._pre_ext(ext, len(pre))
+        if x is None:
+            abi.check(self.lib, self.lib.koordhip_preempt(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
+                                                          abi.ptr(vic, C.c_int32) if max_victims else None, max_victims))
+        else:
+            self._need("koordhip_preempt_ext")
+            abi.check(self.lib, self.lib.koordhip_preempt_ext(self._ctx, pre.ctypes.data, x.ctypes.data, len(pre),
+                                                              out.ctypes.data,
+                                                              abi.ptr(vic, C.c_int32) if max_victims else None,
+                                                              max_victims))
         return out, vic
 
     def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0):
@@ -414,13 +453,20 @@ class PlacementEngine:
                                                              max_victims, st.ctypes.data))
         return out, vic, {f: int(st[f][0]) for f in st.dtype.names}
 
-    def preempt_node_verdicts(self, preemptor) -> np.ndarray:
-        """One preemptor's verdict on every node (abi.PREEMPT_NODE_DTYPE [n])."""
+    def preempt_node_verdicts(self, preemptor, ext=None) -> np.ndarray:
+        """One preemptor's verdict on every node (abi.PREEMPT_NODE_DTYPE [n]).
+        ext: its abi.POD_EXT_DTYPE record (the DeviceShare mode)."""
         pre = np.ascontiguousarray(np.atleast_1d(preemptor), dtype=abi.PREEMPTOR_DTYPE)
         if len(pre) != 1:
             raise ValueError("preempt_node_verdicts takes one preemptor")
         out = np.zeros(self.n, abi.PREEMPT_NODE_DTYPE)
-        abi.check(self.lib, self.lib.koordhip_preempt_node_verdicts(self._ctx, pre.ctypes.data, out.ctypes.data))
+        x = self._pre_ext(ext, 1)
+        if x is None:
+            abi.check(self.lib, self.lib.koordhip_preempt_node_verdicts(self._ctx, pre.ctypes.data, out.ctypes.data))
+        else:
+            self._need("koordhip_preempt_node_verdicts_ext")
+            abi.check(self.lib, self.lib.koordhip_preempt_node_verdicts_ext(self._ctx, pre.ctypes.data, x.ctypes.data,
+                                                                            out.ctypes.data))
         return out
 
     def last_stats(self) -> dict:

@@ -6,6 +6,11 @@ pods that sit on the nodes, the preemptor records and a view of the result.
                        from the PDB objects as preempt.go:222-267 matches them)
     preemptor_records  pending pods + their quotas' postFilterState -> abi.PREEMPTOR_DTYPE
     PreemptionResult   node name + victim pod keys of one preemptor
+    assigned_ext_records / preemptor_ext_records
+                       the dry run under DeviceShare (preempt_set_mode(device=True)):
+                       what the listed pods hold of devices and extended scalars
+                       (abi.ASSIGNED_EXT_DTYPE, beside assigned_records' records) and
+                       the preemptors' koordhip_pod_ext records
 
 With Reservation state (PlacementEngine.preempt_set_mode(resv=True)) pass
 assigned_records the per-node slot order of the snapshot's reservation columns
@@ -170,6 +175,57 @@ def preemptor_records(pods: Iterable[k8s.Pod], profile: Profile, quotas: QuotaId
         rec["q_req"] = _quantities(reqs, resources)
         rec["q_mask"] = sum(1 << d for d, r in enumerate(resources) if r in st.runtime)
     return out
+
+
+def assigned_ext_records(pods: Iterable[k8s.Pod], table, node_index: Dict[str, int]) -> np.ndarray:
+    """abi.ASSIGNED_EXT_DTYPE records beside assigned_records' (the same pods in
+    the same order: those bound to a node of `node_index`), for the dry run
+    under DeviceShare (PlacementEngine.preempt_set_mode(device=True)):
+
+      xreq / xmask          deviceshare.fit_xreq: the extended scalars
+                            NodeInfo.RemovePod / AddPod move
+      dev_slots / dev_per   the device-allocated annotation
+                            (deviceshare.parse_device_allocated), every minor as
+                            the slot of the pod's node in `table`'s dev_minor
+
+    A minor the node does not list is dropped (the reference frees nothing
+    there either: total[minor] is nil).  MarshalError for a pod whose minors of
+    one type hold different amounts: the records carry one per-card amount per
+    type (plugin.go:465-478 allocates that way)."""
+    from . import deviceshare as ds
+    pods = [p for p in pods if p.node_name in node_index]
+    out = np.zeros(len(pods), abi.ASSIGNED_EXT_DTYPE)
+    for j, pod in enumerate(pods):
+        rec = out[j]
+        for name, v in ds.fit_xreq(pod).items():
+            k = ds.XRES_INDEX[name]
+            rec["xreq"][k] = v
+            rec["xmask"] |= 1 << k
+        i = node_index[pod.node_name]
+        for typ, items in ds.parse_device_allocated(pod.annotations).items():
+            if typ not in ds.TYPE_INDEX:
+                raise MarshalError(f"pod {pod.key}: device type {typ!r} is not supported (gpu, rdma, fpga)")
+            t = ds.TYPE_INDEX[typ]
+            per = None
+            for minor, res in items:
+                slots = [s for s in range(table.dev_slots) if int(table["dev_minor"][i, t, s]) == minor]
+                if not slots:
+                    continue
+                amounts = [int(res.get(n, 0)) for n in ds.TYPE_RESOURCES[typ]]
+                if per is not None and amounts != per:
+                    raise MarshalError(f"pod {pod.key}: its {typ} minors hold different amounts ({per} and {amounts}); "
+                                       "the dry run under DeviceShare takes one per-card amount per type")
+                per = amounts
+                rec["dev_slots"][t] |= 1 << slots[0]
+            if per is not None:
+                rec["dev_per"][t, :len(per)] = per
+    return out
+
+
+def preemptor_ext_records(pods: Iterable[k8s.Pod]) -> np.ndarray:
+    """The preemptors' abi.POD_EXT_DTYPE records (deviceshare.pod_ext_records) for preempt(ext=...)."""
+    from . import deviceshare as ds
+    return ds.pod_ext_records(pods)
 
 
 @dataclass
