@@ -1130,8 +1130,9 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *
  * (the plugin in the Filter or Score, reservation columns, resv_dev_slot
  * columns), with or without KOORDHIP_PREEMPT_RESV: that combination needs
  * preemptibleInRRs and tryAllocateFromReservation and is not built;
- * koordhip_preempt_stream (gone victims' devices and scalars would have to
- * leave the call-scoped overlay); what koordhip_preempt refuses besides. */
+ * the plain koordhip_preempt_stream (it takes no koordhip_pod_ext records:
+ * the mode's sequential dry run is koordhip_preempt_stream_ext below); what
+ * koordhip_preempt refuses besides. */
 #define KOORDHIP_PREEMPT_DEVICE 4u
 int koordhip_preempt_set_mode(koordhip_ctx *ctx, uint32_t flags);
 
@@ -1191,6 +1192,37 @@ int koordhip_preempt_stream(koordhip_ctx *ctx, const koordhip_preemptor *pre, in
                             koordhip_preempt_result *out /* [n_pre] */,
                             int32_t *victims /* [n_pre][max_victims], may be NULL */, int32_t max_victims,
                             koordhip_preempt_stream_stats *stats /* may be NULL */);
+/* The sequential dry run in the KOORDHIP_PREEMPT_DEVICE mode (additive to ABI
+ * 15: detect it by the symbol): koordhip_preempt_stream with the preemptors'
+ * koordhip_pod_ext records (ext[p] beside pre[p]; NULL: all empty; the same
+ * check as koordhip_preempt_ext).  S_k is the state above, extended by what the
+ * mode moves:
+ *   - a gone pod is also off xrequested[x] by its xreq[x] over its xmask, and
+ *     for a call with a device preemptor off its node's devices:
+ *     used[t][s][r] -= dev_per[t][r] for every slot s of its dev_slots[t],
+ *     before the walk and for the whole of it (the walk's used - Pd starts
+ *     lower; free stays max0(total - max0(used - Pd)));
+ *   - a nominated pod j with priority_j >= priority_k also has its xreq on
+ *     xrequested over its xmask (NodeInfo.AddPod counts a nominated pod's
+ *     scalars);
+ *   - a nominated pod holds NO devices.  This is the reference's behaviour:
+ *     DeviceShare's AddPod looks the pod up in the node's device cache
+ *     (deviceshare/plugin.go:201-212), a nominated pod has no allocation there
+ *     and the hook returns without touching preemptibleDevices.  Two device
+ *     preemptors can therefore be nominated onto the same freed minor; only the
+ *     scalars (nvidia.com/gpu, ...) keep them apart.
+ * UNRESOLVABLE is the mode's rule on S_k's start row.  For n_pre = 1 the call
+ * is koordhip_preempt_ext.  Accepted only in the KOORDHIP_PREEMPT_DEVICE mode
+ * (with KOORDHIP_PREEMPT_NUMA_FROZEN or without), ext NULL or not; refused as
+ * the mode's other calls are (PodTopologySpread / InterPodAffinity, Reservation
+ * state, reserve / operating-mode preemptors, a communicator,
+ * KOORDHIP_POD_NUMA_ERROR).  Every preemptor is evaluated on every node (the
+ * per-preemptor chain; no block is skipped), so stats is full_recomputes as
+ * above, block_recomputes = n_pre * ceil(n / 256), blocks_skipped = 0. */
+int koordhip_preempt_stream_ext(koordhip_ctx *ctx, const koordhip_preemptor *pre, const koordhip_pod_ext *ext,
+                                int32_t n_pre, koordhip_preempt_result *out /* [n_pre] */,
+                                int32_t *victims /* [n_pre][max_victims], may be NULL */, int32_t max_victims,
+                                koordhip_preempt_stream_stats *stats /* may be NULL */);
 
 /* The same split in two so a caller can time the device part alone: stage
  * (host -> HBM copy) then place (HBM-resident pods, result kept on device

@@ -3831,9 +3831,10 @@ static int preempt_carve(koordhip_ctx *c, void **buf, size_t *cap, size_t align,
 }  // extern "C++"
 
 // The checks the dry-run calls share, and the preemptors' upload (out: where the call's answer goes; stream:
-// koordhip_preempt_stream asks).
+// a sequential dry run asks; stream_ext: it is koordhip_preempt_stream_ext, for which ext may be NULL).
 static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, const void *out,
-                         int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr) {
+                         int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr,
+                         bool stream_ext = false) {
   if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
   const kh::WalkMode mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
@@ -3841,13 +3842,16 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (!c->pre_loaded)
     return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
                                  "load_snapshot)");
+  if (stream_ext && !mode.dev)
+    return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_ext: only in the KOORDHIP_PREEMPT_DEVICE mode, with records or "
+                                 "with ext NULL (elsewhere the sequential dry run is koordhip_preempt_stream)");
   if (mode.dev) {
     // the DEVICE mode: DeviceShare (and the normalized static Scores, which no dry run reads) and nothing else of
     // the sequential cycle
-    if (stream)
+    if (stream && !stream_ext)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "
-                                   "KOORDHIP_PREEMPT_DEVICE (gone victims' devices and extended scalars would have "
-                                   "to leave the call-scoped overlay)");
+                                   "KOORDHIP_PREEMPT_DEVICE (it takes no koordhip_pod_ext records: the sequential dry "
+                                   "run of the DEVICE mode is koordhip_preempt_stream_ext)");
     if ((c->cfg.filter_plugins | c->cfg.score_plugins) & (KOORDHIP_PLUGIN_PTS | KOORDHIP_PLUGIN_IPA))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE not with PodTopologySpread or "
                                    "InterPodAffinity in the profile (they keep AddPod / RemovePod state of their own)");
@@ -3859,8 +3863,8 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   } else if (c->seq || c->seq_profile) {
     if (stream && mode.devp)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "
-                                   "KOORDHIP_PREEMPT_DEVICE (gone victims' devices and extended scalars would have "
-                                   "to leave the call-scoped overlay)");
+                                   "KOORDHIP_PREEMPT_DEVICE (it takes no koordhip_pod_ext records: the sequential dry "
+                                   "run of the DEVICE mode is koordhip_preempt_stream_ext)");
     return fail(KOORDHIP_EINVAL, "koordhip_preempt: the profile / snapshot evaluates in the sequential cycle "
                                  "(DeviceShare, normalized Scores, PodTopologySpread, InterPodAffinity): not covered; "
                                  "a profile whose sequential-cycle plugins are DeviceShare only is accepted after "
@@ -3952,8 +3956,9 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
 // The entry of koordhip_preempt and koordhip_preempt_stream: preempt_ready, then the answer that needs no
 // launch.  With no preemptor or no node the caller returns; without a node nobody has a pick or a victim.
 static int preempt_enter(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
-                         int32_t *victims, int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr) {
-  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream, ext)) return e;
+                         int32_t *victims, int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr,
+                         bool stream_ext = false) {
+  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream, ext, stream_ext)) return e;
   if (n_pre == 0 || c->n > 0) return 0;
   std::memset(out, 0, (size_t)n_pre * sizeof(*out));
   for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
@@ -3998,11 +4003,13 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
 }
 
 // The sequential dry run: every buffer that changes during the call is carved
-// out of d_pre_st and initialised here; the rows, the table and pre_pdb are read only.
-int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
-                            int32_t *victims, int32_t max_victims, koordhip_preempt_stream_stats *stats) {
+// out of d_pre_st and initialised here; the rows, the table and pre_pdb are read only.  stream_ext:
+// koordhip_preempt_stream_ext asks (the DEVICE mode's chain, ext NULL: all-empty records).
+static int preempt_stream_run(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext, int32_t n_pre,
+                              koordhip_preempt_result *out, int32_t *victims, int32_t max_victims,
+                              koordhip_preempt_stream_stats *stats, bool stream_ext) {
   static_assert(sizeof(koordhip_preempt_stream_stats) == 24, "stream stats");
-  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, true)) return e;
+  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, true, ext, stream_ext)) return e;
   if (stats) *stats = koordhip_preempt_stream_stats{};
   if (n_pre == 0 || c->n == 0) return 0;
   const int32_t n = c->n;
@@ -4039,13 +4046,28 @@ int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int3
   if (int e = preempt_inputs(c, n_pre, &in)) return e;
   HIP_TRY(hipMemsetAsync(st.gone, 0, zero_bytes, c->stream));
   HIP_TRY(hipMemsetAsync(st.head, 0xFF, ff_bytes, c->stream));
-  HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, st, max_victims, full,
-                                    in.plane, in.mode, c->stream));
+  if (stream_ext)
+    HIP_TRY(kh::launch_preempt_stream_dev(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, st, max_victims,
+                                          in.plane, in.mode, c->stream, in.dw));
+  else
+    HIP_TRY(kh::launch_preempt_stream(c->dc, c->d, in.tab, in.off, c->pre_pdb, in.dp, n_pre, st, max_victims, full,
+                                      in.plane, in.mode, c->stream));
   HIP_TRY(hipMemcpyAsync(out, st.res, (size_t)n_pre * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   if (nv) HIP_TRY(hipMemcpyAsync(victims, st.victims, nv * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (stats) HIP_TRY(hipMemcpyAsync(stats, st.stats, sizeof(*stats), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+int koordhip_preempt_stream(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
+                            int32_t *victims, int32_t max_victims, koordhip_preempt_stream_stats *stats) {
+  return preempt_stream_run(c, pre, nullptr, n_pre, out, victims, max_victims, stats, false);
+}
+
+int koordhip_preempt_stream_ext(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext, int32_t n_pre,
+                                koordhip_preempt_result *out, int32_t *victims, int32_t max_victims,
+                                koordhip_preempt_stream_stats *stats) {
+  return preempt_stream_run(c, pre, ext, n_pre, out, victims, max_victims, stats, true);
 }
 
 int koordhip_preempt_node_verdicts_ext(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext,

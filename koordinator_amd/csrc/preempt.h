@@ -172,5 +172,13 @@ struct StreamState {
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                  int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s);
+// ... in the DEVICE mode (koordhip_preempt_stream_ext; m.dev 1 or 2, dw as for launch_preempt): the same state
+// and the same answers' layout, built as the per-preemptor chain only: k_preempt_seq_dev on every block,
+// k_preempt_seq_pick, k_preempt_apply_dev.  A gone pod's scalars and devices are read off its second-table
+// record by every later walk; NomEntry k is preemptor k's, whose scalars are dw.px[k]'s.  The stats are those of
+// the chain: block_recomputes = n_pre * blocks, blocks_skipped = 0, full_recomputes as in the plain stream.
+hipError_t launch_preempt_stream_dev(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                                     const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
+                                     int32_t max_victims, const uint64_t *plane, WalkMode m, hipStream_t s, DevWalk dw);
 
 }  // namespace kh

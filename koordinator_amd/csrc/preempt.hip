@@ -47,10 +47,13 @@
 // the plugin's AddPod / RemovePod state (preemptible, preemptibleInRRs:
 // resv.hpp ResvPre) per (preemptor, node) in registers; RS = 1 or
 // KOORDHIP_RESV_SLOTS reservation slots per node.  Not in the stream.
-// DEV > 0 (KOORDHIP_PREEMPT_DEVICE, with RS = 0 and not in the stream): the
+// DEV > 0 (KOORDHIP_PREEMPT_DEVICE, with RS = 0): the
 // listed pods' extended scalars move with them (1), and for a call with a
 // device preemptor so do their devices (2): DeviceShare's preemptibleDevices
-// per (preemptor, node) as used - Pd in LDS, one column per thread.
+// per (preemptor, node) as used - Pd in LDS, one column per thread.  In the
+// stream (koordhip_preempt_stream_ext) these are kernels of their own,
+// k_preempt_seq_dev<NUMA, DEV> / k_preempt_apply_dev<NUMA, DEV>, the chain
+// without phase 1; k_preempt_seq_pick is shared.
 //
 // Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
 // reads the row the previous add / remove left), so a wave would hold 63 idle
@@ -206,6 +209,7 @@ struct DevSide {
   int64_t *u;
   int32_t stride;
   int32_t i, n;
+  const DevPodX *px;  // the call's records (the stream: nominated preemptor e's scalars are px[e]'s; else NULL)
 };
 
 __device__ __forceinline__ int64_t &dev_u(const DevSide &ds, int t, int s, int r) {
@@ -273,6 +277,9 @@ __device__ __forceinline__ bool any_potential(const DevAsg *__restrict__ list, i
 // moves with every listed pod that holds some (its DevAsgX record, read for ASG_HAS_EXT records only).  DEV = 2:
 // and for a device preemptor on a nodeDevice node every move of a listed pod moves the devices it holds into /
 // out of preemptibleDevices, which the DeviceShare Filter of every fit test frees (dev_filter_pre).
+// With OVL (koordhip_preempt_stream_ext): a gone pod's scalars are off xrequested and its devices off used for
+// the whole walk; a nominated preemptor of P's priority and above has its scalars on xrequested (ds.px) and
+// holds no device.
 template <int EMIT, bool OVL, bool NUMA, int RS = 0, int DEV = 0>
 __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, const DevNumaClass *classes, const NV &v,
                                                               const WalkRow<RS> &nr, const DevAsg *__restrict__ list,
@@ -280,7 +287,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
                                                               int32_t *vout, int32_t vmax, const NodeOverlay &ov,
                                                               uint32_t fcode, const DevSide &ds = DevSide{}) {
   static_assert(!(OVL && RS > 0), "the sequential dry run holds no Reservation state");
-  static_assert(DEV == 0 || (!OVL && RS == 0), "the DEVICE mode: not in the stream, not with Reservation state");
+  static_assert(DEV == 0 || RS == 0, "the DEVICE mode: not with Reservation state");
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
   // xfree[j] = Allocatable - Requested of extended scalar j, for P's scalars (DEV > 0); tm: the device types of P
@@ -344,11 +351,28 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       while (g) {
         const int32_t k = (int32_t)__ffsll((unsigned long long)g) - 1 + 64 * h;
         g &= g - 1;
-        if (k < len) apply_delta(w, list[k].pod, -1);
+        if (k >= len) continue;
+        apply_delta(w, list[k].pod, -1);
+        if constexpr (DEV > 0) {  // NodeInfo.RemovePod took a gone pod's scalars off Requested as well
+          if ((list[k].flags & ASG_HAS_EXT) && xm) {
+            const DevAsgX &ax = ds.xlist[k];
+#pragma unroll
+            for (int j = 0; j < KOORDHIP_NXRES; j++)
+              if (((xm & ax.xmask) >> j) & 1u) xfree[j] += ax.xreq[j];
+          }
+        }
       }
     }
-    for (int32_t e = ov.head; e >= 0; e = ov.nom[e].next)
-      if (ov.nom[e].prio >= pprio) apply_delta(w, ov.nom[e].pod, +1);
+    for (int32_t e = ov.head; e >= 0; e = ov.nom[e].next) {
+      if (ov.nom[e].prio < pprio) continue;
+      apply_delta(w, ov.nom[e].pod, +1);
+      if constexpr (DEV > 0) {  // NodeInfo.AddPod counts a nominated pod's scalars (entry e is preemptor e's)
+        const DevPodX &nx = ds.px[e];
+#pragma unroll
+        for (int j = 0; j < KOORDHIP_NXRES; j++)
+          if (((xm & nx.xmask) >> j) & 1u) xfree[j] -= nx.xreq[j];
+      }
+    }
   }
   if constexpr (NUMA) {
     if (fcode) {
@@ -387,6 +411,29 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         for (int s = 0; s < DS; s++)
 #pragma unroll
           for (int rr = 0; rr < DR; rr++) dev_u(ds, t, s, rr) = s < dv.slots ? dv.used[a0 + (size_t)s * DR + rr] : 0;
+      }
+    }
+    if constexpr (OVL) {
+      // the gone pods hold no device any more: used - Pd starts lower, for the whole walk.  A nominated pod holds
+      // none either (DeviceShare's AddPod finds no allocation of it in the node's device cache).
+      for (int h = 0; h < 2 && tm; h++) {
+        uint64_t g = h ? ov.g1 : ov.g0;
+        while (g) {
+          const int32_t k = (int32_t)__ffsll((unsigned long long)g) - 1 + 64 * h;
+          g &= g - 1;
+          if (k >= len || !(list[k].flags & ASG_HAS_EXT)) continue;
+          const DevAsgX &ax = ds.xlist[k];
+#pragma unroll
+          for (int t = 0; t < DT; t++) {
+            const uint32_t sl = ((tm >> t) & 1u) ? ax.dev_slots[t] : 0u;
+            if (!sl) continue;
+#pragma unroll
+            for (int s = 0; s < DS; s++)
+              if ((sl >> s) & 1u)
+#pragma unroll
+                for (int rr = 0; rr < DR; rr++) dev_u(ds, t, s, rr) -= ax.dev_per[t][rr];
+          }
+        }
       }
     }
   }
@@ -628,6 +675,7 @@ __device__ __forceinline__ DevSide dev_side(const DevNodes &d, const DevAsgX *xl
   ds.stride = THREADS;
   ds.i = i;
   ds.n = d.n;
+  ds.px = nullptr;
   return ds;
 }
 
@@ -1056,6 +1104,125 @@ __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, co
   }
 }
 
+// ... in the DEVICE mode (koordhip_preempt_stream_ext): the per-preemptor chain only, every block evaluates
+// preemptor k on the state its predecessors left (there is no phase 1 and nothing is skipped; StreamFlags::full
+// is set, touched is written and never read).  DEV = 2 keeps the 256-thread block and dev_state's
+// su[t][s][r][thread]: one partial per 256 nodes, so k_preempt_seq_pick and the carve are the plain stream's.
+template <bool NUMA, int DEV>
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq_dev(DevCfg cfg, DevNodes d,
+                                                                     const DevAsg *__restrict__ tab,
+                                                                     const int32_t *__restrict__ off,
+                                                                     const DevPre *__restrict__ pre, int32_t k,
+                                                                     StreamState st, NumaPlane pl, DevWalk dw) {
+  const int t = threadIdx.x, wave = t >> 6;
+  const int32_t b = (int32_t)blockIdx.x, nb = (int32_t)gridDim.x;
+  if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.stats->block_recomputes), 1ull);
+  const DevCfg c = envelope<NUMA, 0, DEV>(cfg);
+  int64_t *su = dev_state<DEV, PREEMPT_THREADS>();
+  __shared__ int32_t scnt[KOORDHIP_PREEMPT_STATUSES];
+  __shared__ PreemptPartial sbest[PRE_WAVES];
+  if (t < KOORDHIP_PREEMPT_STATUSES) scnt[t] = 0;
+  __syncthreads();
+  const DevPre P = stream_pre(pre, st, k);
+  const PdbAllowed pdb = *st.pdb;
+  const int32_t i = b * PREEMPT_THREADS + t;
+  const bool live = i < d.n;
+  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, live, dw.xtab);
+  koordhip_preempt_node r{};
+  uint32_t fcode = 0u;
+  if constexpr (NUMA) fcode = plane_code(pl, k, i);
+  if (live) {
+    const DevPodX *px = static_cast<const DevPodX *>(dw.px);
+    DevSide ds = dev_side<PREEMPT_THREADS>(d, nd.xlist, px + k, su, i);
+    ds.px = px;
+    r = preempt_node<EMIT_NONE, true, NUMA, 0, DEV>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, nullptr, 0,
+                                                    overlay_of(st, i), fcode, ds);
+  }
+  wave_vote(r, i, live, scnt, &sbest[wave]);
+  __syncthreads();
+  if (t == 0) st.part[(size_t)k * nb + b] = block_best(sbest);
+  if (t < KOORDHIP_PREEMPT_STATUSES) st.bcnt[((size_t)k * nb + b) * KOORDHIP_PREEMPT_STATUSES + t] = scnt[t];
+}
+
+// One wave: k_preempt_apply with the DEVICE mode's walk (DEV = 2: the 64-thread dev_state beside the staged
+// list; lane 0 reads the chosen node's second-table records where they lie).  What the victims held of scalars
+// and devices needs no state of its own: every later walk reads it off the gone positions' records.
+template <bool NUMA, int DEV>
+__global__ __launch_bounds__(64) void k_preempt_apply_dev(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                          const int32_t *__restrict__ off,
+                                                          const DevPre *__restrict__ pre, int32_t n_pre, int32_t k,
+                                                          StreamState st, int32_t vmax, DevWalk dw) {
+  const DevCfg c = envelope<NUMA, 0, DEV>(cfg);
+  int64_t *su = dev_state<DEV, 64>();
+  const int lane = threadIdx.x;
+  const int32_t i = st.res[k].node;
+  if (i < 0 || i >= d.n) return;
+  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, true, dw.xtab);
+  __shared__ uint4 slist[KOORDHIP_PREEMPT_NODE_PODS * ASG_VEC];
+  const uint4 *src = reinterpret_cast<const uint4 *>(nd.list);
+  for (int32_t w = lane; w < nd.len * ASG_VEC; w += 64) slist[w] = src[w];
+  __syncthreads();
+  const DevAsg *list = reinterpret_cast<const DevAsg *>(slist);
+  const DevPre P = stream_pre(pre, st, k);
+  __shared__ int32_t sfreed;
+  __shared__ int64_t ssum[KOORDHIP_PREEMPT_QRES];
+  if (lane == 0) {
+    PdbAllowed pdb = *st.pdb;
+    const DevPodX *px = static_cast<const DevPodX *>(dw.px);
+    DevSide ds = dev_side<64>(d, nd.xlist, px + k, su, i);
+    ds.px = px;
+    // Entry k (preemptor k's: its scalars are px[k]'s) is written before the walk and linked after it: the walk
+    // follows head[i], which does not reach it, and P.pod kept over the DEV = 2 walk would be a scratch frame.
+    NomEntry ne;
+    ne.pod = P.pod;
+    ne.prio = P.prio;
+    ne.next = st.head[i];
+    st.nom[k] = ne;
+    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA, 0, DEV>(
+        c, d.nu.cls, nd.v, nd.nr, list, nd.len, pdb, P, st.vpos, KOORDHIP_PREEMPT_NODE_PODS, overlay_of(st, i), 0u, ds);
+    const int32_t nv = r.status == KOORDHIP_PREEMPT_CANDIDATE ? min(r.n_victims, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
+    uint64_t g0 = 0, g1 = 0;
+    int64_t sum[KOORDHIP_PREEMPT_QRES] = {};
+    bool moved = false;
+    for (int32_t e = 0; e < nv; e++) {
+      const int32_t pos = st.vpos[e];
+      const DevAsg &a = list[pos];
+      if (st.victims && e < vmax) st.victims[(size_t)k * vmax + e] = a.idx;
+      if (pos < 64) g0 |= 1ull << pos; else g1 |= 1ull << (pos - 64);
+      const uint32_t pm = a.pdb_mask;
+      for (int bb = 0; bb < KOORDHIP_PREEMPT_PDBS; bb++)
+        if (((pm >> bb) & 1u) && pdb.a[bb] > 0) {
+          pdb.a[bb]--;
+          moved = true;
+        }
+      if (a.flags & KOORDHIP_ASG_IN_QUOTA)
+        for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) sum[q] += a.qreq[q];
+    }
+    st.gone[2 * (size_t)i] |= g0;
+    st.gone[2 * (size_t)i + 1] |= g1;
+    st.head[i] = k;
+    st.touched[i / PREEMPT_THREADS] = 1;
+    if (moved) {
+      *st.pdb = pdb;
+      st.flags->pdb = 1;
+    }
+    int64_t any = 0;
+    for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) {
+      ssum[q] = sum[q];
+      any |= sum[q];
+    }
+    sfreed = any != 0;
+  }
+  __syncthreads();
+  const int32_t quota = P.quota;
+  if (quota < 0 || !sfreed) return;
+  for (int32_t j = k + 1 + lane; j < n_pre; j += 64) {
+    if (pre[j].quota != quota) continue;
+    for (int q = 0; q < KOORDHIP_PREEMPT_QRES; q++) st.freed[(size_t)j * KOORDHIP_PREEMPT_QRES + q] += ssum[q];
+    st.qflag[j] = 1;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // host-side launch wrappers
 
@@ -1185,6 +1352,30 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
       hipLaunchKernelGGL(k_preempt_seq<NUMA>, blocks, threads, 0, s, c, d, tab, off, pre, k, st, pl);
       hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), wave, 0, s, nb, k, st);
       hipLaunchKernelGGL(k_preempt_apply<NUMA>, dim3(1), wave, 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
+    }
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_preempt_stream_dev(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
+                                     const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
+                                     int32_t max_victims, const uint64_t *plane, WalkMode m, hipStream_t s, DevWalk dw) {
+  if (n_pre <= 0 || d.n <= 0) return hipSuccess;
+  if (m.dev <= 0 || !preempt_profile_ok(c, m, plane, dw)) return hipErrorInvalidValue;
+  const int32_t nb = preempt_blocks(d.n);
+  const NumaPlane pl{plane, (d.n + 63) / 64};
+  StreamFlags fl{};
+  fl.full = 1;  // the chain: every block, every preemptor
+  hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, s, pdb, fl, st);
+  with_walk_dev(m, [&](auto numa, auto dev) {
+    constexpr bool NUMA = decltype(numa)::value;
+    constexpr int DEV = decltype(dev)::value;
+    const dim3 blocks(nb), threads(PREEMPT_THREADS), wave(64);
+    for (int32_t k = 0; k < n_pre; k++) {
+      hipLaunchKernelGGL((k_preempt_seq_dev<NUMA, DEV>), blocks, threads, 0, s, c, d, tab, off, pre, k, st, pl, dw);
+      hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), wave, 0, s, nb, k, st);
+      hipLaunchKernelGGL((k_preempt_apply_dev<NUMA, DEV>), dim3(1), wave, 0, s, c, d, tab, off, pre, n_pre, k, st,
+                         max_victims, dw);
     }
   });
   return hipGetLastError();

@@ -381,6 +381,8 @@ class PlacementEngine:
         if not hasattr(self.lib, symbol):
             raise RuntimeError(f"this libkoordhip build has no {symbol}")
 
+    EXT_NULL = object()   # preempt_stream(ext=EXT_NULL): koordhip_preempt_stream_ext with ext == NULL
+
     def _pre_ext(self, ext, n: int):
         if ext is None:
             return None
@@ -405,7 +407,8 @@ class PlacementEngine:
         and devices are freed in the walk (preempt_load_pods(ext=...), the
         preemptors' records as preempt(ext=...)); refused on a profile without
         DeviceShare, with PodTopologySpread / InterPodAffinity or Reservation
-        state, and by preempt_stream().
+        state, and by preempt_stream() without ext (preempt_stream(ext=...) is
+        the mode's sequential dry run).
         The mode is the context's; False restores the refusal.  flags: the raw
         abi.PREEMPT_* word instead."""
         if not hasattr(self.lib, "koordhip_preempt_set_mode"):
@@ -436,21 +439,33 @@ class PlacementEngine:
                                                               max_victims))
         return out, vic
 
-    def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0):
+    def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0, ext=None):
         """The dry run of a batch whose answers hold together: the preemptors
         are processed in input order, each on the state the earlier ones left
         (their victims gone, they themselves nominated on their nodes, PDB
         budgets and their quotas' used lowered; include/koordhip.h).  Every
         q_used is as of the start of the call.  Returns (results, victims,
         stats) with stats a dict of koordhip_preempt_stream_stats.  Writes no
-        engine state and leaves the loaded table as it was."""
+        engine state and leaves the loaded table as it was.  ext: the
+        preemptors' abi.POD_EXT_DTYPE records: koordhip_preempt_stream_ext, the
+        sequential dry run of the DeviceShare mode (gone victims' scalars and
+        devices are off their nodes, nominated preemptors' scalars on them and
+        a nominated pod holds no device); EXT_NULL: that call with all-empty
+        records; None: the plain call, which a DeviceShare profile refuses."""
         pre = np.ascontiguousarray(np.atleast_1d(preemptors), dtype=abi.PREEMPTOR_DTYPE)
         out = np.zeros(len(pre), abi.PREEMPT_RESULT_DTYPE)
         vic = np.full((len(pre), max_victims), -1, np.int32)
         st = np.zeros(1, abi.PREEMPT_STREAM_STATS_DTYPE)
-        abi.check(self.lib, self.lib.koordhip_preempt_stream(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
-                                                             abi.ptr(vic, C.c_int32) if max_victims else None,
-                                                             max_victims, st.ctypes.data))
+        pv = abi.ptr(vic, C.c_int32) if max_victims else None
+        if ext is None:
+            abi.check(self.lib, self.lib.koordhip_preempt_stream(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
+                                                                 pv, max_victims, st.ctypes.data))
+        else:
+            self._need("koordhip_preempt_stream_ext")
+            x = None if ext is self.EXT_NULL else self._pre_ext(ext, len(pre))
+            abi.check(self.lib, self.lib.koordhip_preempt_stream_ext(self._ctx, pre.ctypes.data,
+                                                                     None if x is None else x.ctypes.data, len(pre),
+                                                                     out.ctypes.data, pv, max_victims, st.ctypes.data))
         return out, vic, {f: int(st[f][0]) for f in st.dtype.names}
 
     def preempt_node_verdicts(self, preemptor, ext=None) -> np.ndarray:
