@@ -1081,7 +1081,8 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *
  * skip them at :255,293, but NodeInfo.RemovePod would still move the restored
  * row): they are never potential victims.  Still KOORDHIP_EINVAL: reserve and
  * operating-mode preemptors; koordhip_preempt_stream on Reservation state, flag
- * or not (earlier victims would have to leave the reservations' Allocated);
+ * or not (earlier victims have to leave the reservations' Allocated: the mode's
+ * sequential dry run is koordhip_preempt_stream_resv below);
  * with NodeNUMAResource in the Filter the flag without
  * KOORDHIP_PREEMPT_NUMA_FROZEN, and both flags on a snapshot loaded with
  * resv_cpus (the frozen verdict does not model the restore of reserved CPUs).
@@ -1223,6 +1224,57 @@ int koordhip_preempt_stream_ext(koordhip_ctx *ctx, const koordhip_preemptor *pre
                                 int32_t n_pre, koordhip_preempt_result *out /* [n_pre] */,
                                 int32_t *victims /* [n_pre][max_victims], may be NULL */, int32_t max_victims,
                                 koordhip_preempt_stream_stats *stats /* may be NULL */);
+/* The sequential dry run in the KOORDHIP_PREEMPT_RESV mode (additive to ABI 15:
+ * detect it by the symbol): koordhip_preempt_stream's inputs, records, victims
+ * layout, stats and error codes, on a context with Reservation state.  It is a
+ * call of its own because koordhip_preempt_stream keeps its refusal there.  S_k
+ * is the state above; for (preemptor k, node) the RESV mode's walk changes so:
+ *   - a gone listed pod bound to slot q (KOORDHIP_ASG_RESV_SLOT) has left its
+ *     reservation (RemoveAssignedPod, frameworkext/reservation_info.go:308-319):
+ *     Allocated[q][c] = max(0, Allocated[q][c] - req[c]) for c in {cpu, memory}
+ *     where the slot holds c (KOORDHIP_RESV_KEY_*), the assigned count drops by
+ *     one, floored at 0;
+ *   - class, restore and the frozen podRequested are those of the lowered
+ *     slots: a class-2 slot whose last assigned pod is gone becomes class 0 and
+ *     its restore no longer happens; a Restricted slot holds more; rRemained
+ *     and the matched Allocated move;
+ *   - a slot with KOORDHIP_RESV_ALLOCATE_ONCE that had an assigned pod when the
+ *     call began stays class 0 for the whole call (the reference's controller
+ *     marks it Succeeded, reservation/controller/controller.go:245-247; the
+ *     engine keeps no phase, so this is the rule);
+ *   - order at the walk's start: the gone pods come off the row and the slots,
+ *     then the restore, then podRequested is frozen (WITHOUT any nominated pod:
+ *     nominated pods are not in the snapshot NodeInfo, transformer.go:129), only
+ *     then the nominated pods with priority_j >= priority_k go onto the row;
+ *     fitsNode's ephemeral-storage and batch amounts are the loaded row's
+ *     without the gone pods;
+ *   - a nominated pod moves the plugin's state at every fit test (upstream's
+ *     addNominatedPods clones the cycle state and runs AddPod, which for a pod
+ *     without a reservation-allocated annotation lowers preemptible[node],
+ *     plugin.go:270-276): with N the summed requests of the qualifying
+ *     nominated pods over the five resources the test reads Pn_eff = max(0, Pn -
+ *     N) in place of Pn (present iff some resource is non-zero); the walk's own
+ *     Pn and every Pr[q] are untouched; a nominated pod is bound to no slot;
+ *   - two passes (RunFilterPluginsWithNominatedPods): on a node with at least
+ *     one qualifying nominated pod "P fits" is T(row with them, Pn_eff) and then
+ *     T(row without them, Pn); the second can fail where the first passes (a
+ *     Default slot is insufficient only while something preemptible is present;
+ *     the branch without a matched reservation calls fitsNode only then).
+ * UNRESOLVABLE is the RESV mode's rule on S_k's start row with the qualifying
+ * nominated pods on it.  For n_pre = 1 the call is koordhip_preempt in the same
+ * mode.  Accepted exactly where koordhip_preempt is in the RESV mode: the flag
+ * set on a context with Reservation state, with NodeNUMAResource in the Filter
+ * KOORDHIP_PREEMPT_NUMA_FROZEN as well, at most KOORDHIP_RESV_SLOTS slots.
+ * KOORDHIP_EINVAL (the context stays usable): the flag missing; no Reservation
+ * state (the sequential dry run there is koordhip_preempt_stream);
+ * KOORDHIP_PREEMPT_DEVICE set; both flags on a resv_cpus snapshot; reserve /
+ * operating-mode preemptors; a communicator; a sequential-cycle snapshot.
+ * Built as the per-preemptor chain: stats is full_recomputes as above,
+ * block_recomputes = n_pre * ceil(n / 256), blocks_skipped = 0. */
+int koordhip_preempt_stream_resv(koordhip_ctx *ctx, const koordhip_preemptor *pre, int32_t n_pre,
+                                 koordhip_preempt_result *out /* [n_pre] */,
+                                 int32_t *victims /* [n_pre][max_victims], may be NULL */, int32_t max_victims,
+                                 koordhip_preempt_stream_stats *stats /* may be NULL */);
 
 /* The same split in two so a caller can time the device part alone: stage
  * (host -> HBM copy) then place (HBM-resident pods, result kept on device

@@ -411,7 +411,7 @@ ADDITIVE_SYMBOLS = ("koordhip_diagnose_ext", "koordhip_node_status_ext", "koordh
                     "koordhip_node_reasons", "koordhip_fetch_reasons", "koordhip_fetch_node_reasons",
                     "koordhip_diagnose_reasons_ext", "koordhip_node_reasons_ext", "koordhip_preempt_set_mode",
                     "koordhip_preempt_load_pods_ext", "koordhip_preempt_ext", "koordhip_preempt_node_verdicts_ext",
-                    "koordhip_preempt_stream_ext")
+                    "koordhip_preempt_stream_ext", "koordhip_preempt_stream_resv")
 
 
 def load_library(path: str = LIB_PATH):
@@ -476,6 +476,7 @@ def load_library(path: str = LIB_PATH):
         "koordhip_preempt_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp, _i32p, C.c_int32]),
         "koordhip_preempt_node_verdicts_ext": (C.c_int, [vp, vp, vp, vp]),
         "koordhip_preempt_stream_ext": (C.c_int, [vp, vp, vp, C.c_int32, vp, _i32p, C.c_int32, vp]),
+        "koordhip_preempt_stream_resv": (C.c_int, [vp, vp, C.c_int32, vp, _i32p, C.c_int32, vp]),
         "koordhip_read_numa": (C.c_int, [vp, _u64p, _u64p, _u64p, _i32p]),
         "koordhip_read_numa_zones": (C.c_int, [vp, _i64p]),
         "koordhip_read_reservations": (C.c_int, [vp, _i64p, _i32p]),
@@ -517,7 +518,7 @@ EXPORTED_SYMBOLS = [
     "koordhip_preempt_load_pods", "koordhip_preempt", "koordhip_preempt_node_verdicts",
     "koordhip_preempt_stream", "koordhip_preempt_set_mode",
     "koordhip_preempt_load_pods_ext", "koordhip_preempt_ext", "koordhip_preempt_node_verdicts_ext",
-    "koordhip_preempt_stream_ext",
+    "koordhip_preempt_stream_ext", "koordhip_preempt_stream_resv",
     "koordhip_fetch_cpusets", "koordhip_read_numa", "koordhip_read_numa_zones", "koordhip_read_reservations",
     "koordhip_read_resv_cpus", "koordhip_read_resv_devices", "koordhip_read_resv_scalars", "koordhip_last_stats", "koordhip_last_kernel_stats",
     "koordhip_set_profile_kernels", "koordhip_last_kernel_names",

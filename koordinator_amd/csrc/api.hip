@@ -3831,10 +3831,11 @@ static int preempt_carve(koordhip_ctx *c, void **buf, size_t *cap, size_t align,
 }  // extern "C++"
 
 // The checks the dry-run calls share, and the preemptors' upload (out: where the call's answer goes; stream:
-// a sequential dry run asks; stream_ext: it is koordhip_preempt_stream_ext, for which ext may be NULL).
+// a sequential dry run asks; stream_ext: it is koordhip_preempt_stream_ext, for which ext may be NULL;
+// stream_resv: it is koordhip_preempt_stream_resv, accepted exactly where koordhip_preempt is in the RESV mode).
 static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, const void *out,
                          int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr,
-                         bool stream_ext = false) {
+                         bool stream_ext = false, bool stream_resv = false) {
   if (!c || ((!pre || !out) && n_pre > 0)) return fail(KOORDHIP_EINVAL, "NULL argument");
   if (n_pre < 0 || max_victims < 0) return fail(KOORDHIP_EINVAL, "n_pre / max_victims < 0");
   const kh::WalkMode mode = kh::preempt_walk_mode(c->dc, c->pre_mode);
@@ -3845,6 +3846,17 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (stream_ext && !mode.dev)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_ext: only in the KOORDHIP_PREEMPT_DEVICE mode, with records or "
                                  "with ext NULL (elsewhere the sequential dry run is koordhip_preempt_stream)");
+  if (stream_resv) {
+    if (c->pre_mode & KOORDHIP_PREEMPT_DEVICE)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_resv: not in the KOORDHIP_PREEMPT_DEVICE mode (DeviceShare "
+                                   "beside Reservation state is the follow-up, not built)");
+    if (!mode.resv && !(c->seq || c->seq_profile))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_resv: the context has no Reservation plugin state (the "
+                                   "sequential dry run there is koordhip_preempt_stream)");
+    if (mode.resv && !mode.rs)
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_resv: only in the KOORDHIP_PREEMPT_RESV mode "
+                                   "(koordhip_preempt_set_mode)");
+  }
   if (mode.dev) {
     // the DEVICE mode: DeviceShare (and the normalized static Scores, which no dry run reads) and nothing else of
     // the sequential cycle
@@ -3861,7 +3873,7 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
                                    "KOORDHIP_PREEMPT_RESV: that combination (preemptibleInRRs, "
                                    "tryAllocateFromReservation) is the follow-up, not built");
   } else if (c->seq || c->seq_profile) {
-    if (stream && mode.devp)
+    if (stream && !stream_resv && mode.devp)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "
                                    "KOORDHIP_PREEMPT_DEVICE (it takes no koordhip_pod_ext records: the sequential dry "
                                    "run of the DEVICE mode is koordhip_preempt_stream_ext)");
@@ -3893,10 +3905,11 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
                                  "PreFilterExtensions: its state does not move in a dry run) unless "
                                  "koordhip_preempt_set_mode(KOORDHIP_PREEMPT_NUMA_FROZEN) accepted that");
   if (mode.resv) {
-    if (stream)
+    if (stream && !stream_resv)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not with Reservation plugin state, with or without "
                                    "KOORDHIP_PREEMPT_RESV (earlier preemptors' victims would have to leave the "
-                                   "reservations' Allocated and assigned counts)");
+                                   "reservations' Allocated and assigned counts: the sequential dry run of the RESV "
+                                   "mode is koordhip_preempt_stream_resv)");
     if (!mode.rs)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: not with Reservation plugin state (its AddPod / RemovePod state is "
                                    "not kept) unless koordhip_preempt_set_mode(KOORDHIP_PREEMPT_RESV) asked for it");
@@ -3957,8 +3970,8 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
 // launch.  With no preemptor or no node the caller returns; without a node nobody has a pick or a victim.
 static int preempt_enter(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre, koordhip_preempt_result *out,
                          int32_t *victims, int32_t max_victims, bool stream, const koordhip_pod_ext *ext = nullptr,
-                         bool stream_ext = false) {
-  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream, ext, stream_ext)) return e;
+                         bool stream_ext = false, bool stream_resv = false) {
+  if (int e = preempt_ready(c, pre, n_pre, out, max_victims, stream, ext, stream_ext, stream_resv)) return e;
   if (n_pre == 0 || c->n > 0) return 0;
   std::memset(out, 0, (size_t)n_pre * sizeof(*out));
   for (int32_t p = 0; p < n_pre; p++) out[p].node = -1;
@@ -4004,12 +4017,13 @@ int koordhip_preempt(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_p
 
 // The sequential dry run: every buffer that changes during the call is carved
 // out of d_pre_st and initialised here; the rows, the table and pre_pdb are read only.  stream_ext:
-// koordhip_preempt_stream_ext asks (the DEVICE mode's chain, ext NULL: all-empty records).
+// koordhip_preempt_stream_ext asks (the DEVICE mode's chain, ext NULL: all-empty records); stream_resv:
+// koordhip_preempt_stream_resv does (the RESV mode's chain: launch_preempt_stream with the mode's slots).
 static int preempt_stream_run(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext, int32_t n_pre,
                               koordhip_preempt_result *out, int32_t *victims, int32_t max_victims,
-                              koordhip_preempt_stream_stats *stats, bool stream_ext) {
+                              koordhip_preempt_stream_stats *stats, bool stream_ext, bool stream_resv = false) {
   static_assert(sizeof(koordhip_preempt_stream_stats) == 24, "stream stats");
-  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, true, ext, stream_ext)) return e;
+  if (int e = preempt_enter(c, pre, n_pre, out, victims, max_victims, true, ext, stream_ext, stream_resv)) return e;
   if (stats) *stats = koordhip_preempt_stream_stats{};
   if (n_pre == 0 || c->n == 0) return 0;
   const int32_t n = c->n;
@@ -4068,6 +4082,12 @@ int koordhip_preempt_stream_ext(koordhip_ctx *c, const koordhip_preemptor *pre, 
                                 koordhip_preempt_result *out, int32_t *victims, int32_t max_victims,
                                 koordhip_preempt_stream_stats *stats) {
   return preempt_stream_run(c, pre, ext, n_pre, out, victims, max_victims, stats, true);
+}
+
+int koordhip_preempt_stream_resv(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t n_pre,
+                                 koordhip_preempt_result *out, int32_t *victims, int32_t max_victims,
+                                 koordhip_preempt_stream_stats *stats) {
+  return preempt_stream_run(c, pre, nullptr, n_pre, out, victims, max_victims, stats, false, true);
 }
 
 int koordhip_preempt_node_verdicts_ext(koordhip_ctx *c, const koordhip_preemptor *pre, const koordhip_pod_ext *ext,

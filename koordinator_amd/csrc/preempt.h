@@ -167,8 +167,11 @@ struct StreamState {
 // a tile of 32 at a time) and per preemptor k: k_preempt_seq (the blocks that
 // have to evaluate k again), k_preempt_seq_pick, k_preempt_apply.  full: the
 // A/B knob, every block evaluates every preemptor again.  plane, m: as for
-// launch_preempt, the plane written once before the first preemptor; m.rs is 0
-// (the sequential dry run holds no Reservation state).  Nothing synchronises.
+// launch_preempt, the plane written once before the first preemptor.  With
+// m.rs > 0 (koordhip_preempt_stream_resv) the walk carries the node's
+// reservation slots, lowered per walk by the gone positions' records, and the
+// call is built as the per-preemptor chain only: no phase 1, `full` forced,
+// the stats those of launch_preempt_stream_dev.  Nothing synchronises.
 hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                  int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s);

@@ -28,7 +28,7 @@
 //   k_preempt_victims<NUMA, RS>
 //                     one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
-//   k_preempt_blk<NUMA> / k_preempt_seq<NUMA> / k_preempt_seq_pick / k_preempt_apply<NUMA>
+//   k_preempt_blk<NUMA> / k_preempt_seq<NUMA, RS> / k_preempt_seq_pick / k_preempt_apply<NUMA, RS>
 //                     the sequential dry run (koordhip_preempt_stream): the
 //                     preemptors in input order, each on the state the earlier
 //                     ones left (victims gone, preemptors nominated, budgets
@@ -46,7 +46,11 @@
 // starts from the row after the cycle's restore for the preemptor and keeps
 // the plugin's AddPod / RemovePod state (preemptible, preemptibleInRRs:
 // resv.hpp ResvPre) per (preemptor, node) in registers; RS = 1 or
-// KOORDHIP_RESV_SLOTS reservation slots per node.  Not in the stream.
+// KOORDHIP_RESV_SLOTS reservation slots per node.  In the stream
+// (koordhip_preempt_stream_resv) k_preempt_seq / k_preempt_apply take the same
+// RS, run as the chain without phase 1: a walk lowers its copy of the slots by
+// the gone pods and runs both passes of RunFilterPluginsWithNominatedPods on a
+// node with a nominated pod (preempt_node, OVL with RS > 0).
 // DEV > 0 (KOORDHIP_PREEMPT_DEVICE, with RS = 0): the
 // listed pods' extended scalars move with them (1), and for a call with a
 // device preemptor so do their devices (2): DeviceShare's preemptibleDevices
@@ -190,8 +194,46 @@ constexpr int EMIT_NONE = 0, EMIT_IDX = 1, EMIT_POS = 2;
 // BeforePreFilter restored), the slots and nodeRState.podRequested stay as they
 // are and every move of a listed pod also moves the plugin's AddPod /
 // RemovePod state (resv.hpp ResvPre), which filterWithReservations reads in
-// every fit test.  Not with OVL: the stream refuses Reservation state.
+// every fit test.
+//
+// OVL with RS > 0 (koordhip_preempt_stream_resv), in this order: the gone pods come off the row
+// and off the walk's copy of the slots (resv_unassign); the restore and the frozen podRequested are those of the
+// lowered slots, taken before any nominated pod is on the row; then the nominated pods of P's priority and above
+// join the row.  On a node with such a pod every fit test is RunFilterPluginsWithNominatedPods' two passes: the row
+// with them and preemptible[node] lowered by their requests (AddPod on the cloned state), then the row without
+// them (NomSum) and the walk's own state.
 constexpr uint32_t NUMA_F_FAIL = 1u, NUMA_F_UNRESOLVABLE = 2u;
+
+// What a node's qualifying nominated pods add to its row, summed (n: how many), so that the second pass can
+// take them off again.  Every amount is an integer below 2^53 held as f64: the sums are exact in any order.  (The
+// LoadAware estimates apply_delta also moves are not kept: the Filter reads the row's threshold bits, never them.)
+struct NomSum {
+  double r[KOORDHIP_NRES];
+  double nz_cpu, nz_mem;
+  int32_t n;
+};
+
+__device__ __forceinline__ void nom_add(NomSum &s, const DevPod &p) {
+#pragma unroll
+  for (int k = 0; k < KOORDHIP_NRES; k++) s.r[k] += p.req[k];
+  s.nz_cpu += p.nz_cpu_m;
+  s.nz_mem += p.nz_mem;
+  s.n++;
+}
+
+// apply_delta(-1) of all of them at once, for a Filter
+__device__ __forceinline__ void nom_off(NV &v, const NomSum &s) {
+#pragma unroll
+  for (int k = 0; k < KOORDHIP_NRES; k++) v.r[k] -= s.r[k];
+  v.nz_cpu -= s.nz_cpu;
+  v.nz_mem -= s.nz_mem;
+  v.npods -= s.n;
+  uint32_t f = v.flags & ~(NF_OVER_CPU | NF_OVER_MEM | NF_OVER_EPH);
+  if (v.r[KOORDHIP_RES_CPU] > v.a[KOORDHIP_RES_CPU]) f |= NF_OVER_CPU;
+  if (v.r[KOORDHIP_RES_MEM] > v.a[KOORDHIP_RES_MEM]) f |= NF_OVER_MEM;
+  if (v.r[KOORDHIP_RES_EPH] > v.a[KOORDHIP_RES_EPH]) f |= NF_OVER_EPH;
+  v.flags = f;
+}
 
 template <int RS>
 using WalkRow = NumaRowRS<(RS > 0 ? RS : 1)>;
@@ -286,10 +328,15 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
                                                               int32_t *vout, int32_t vmax, const NodeOverlay &ov,
                                                               uint32_t fcode, const DevSide &ds = DevSide{}) {
-  static_assert(!(OVL && RS > 0), "the sequential dry run holds no Reservation state");
   static_assert(DEV == 0 || RS == 0, "the DEVICE mode: not with Reservation state");
+  constexpr bool SEQ_RS = OVL && RS > 0;  // koordhip_preempt_stream_resv
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
+  // SEQ_RS: the walk's own copies, v0 the loaded row without the gone pods and sl the slots they have left
+  // (elsewhere the caller's, untouched)
+  std::conditional_t<SEQ_RS, NV, const NV &> v0 = v;
+  std::conditional_t<SEQ_RS, WalkRow<RS>, const WalkRow<RS> &> sl = nr;
+  NomSum ns{};
   // xfree[j] = Allocatable - Requested of extended scalar j, for P's scalars (DEV > 0); tm: the device types of P
   // whose preemptible state the walk keeps (DEV = 2; 0: DeviceShare passes whatever is removed)
   int64_t xfree[KOORDHIP_NXRES] = {};
@@ -337,16 +384,53 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   int nmatch = 0;
   uint32_t mm = 0u;
   ResvPre<(RS > 0 ? RS : 1)> rp;
-  if constexpr (RS > 0) {
-    if (c.resv) nmatch = resv_restore(w, nr, pod, mm);
-    resv_pre_init(rp, w, nr, pod, mm);
+  if constexpr (SEQ_RS) {
+    // the gone pods come off the row and the slots before the restore: class, restore and podRequested are those
+    // of the lowered slots
+    for (int h = 0; h < 2; h++) {
+      uint64_t g = h ? ov.g1 : ov.g0;
+      while (g) {
+        const int32_t k = (int32_t)__ffsll((unsigned long long)g) - 1 + 64 * h;
+        g &= g - 1;
+        if (k >= len) continue;
+        apply_delta(v0, list[k].pod, -1);
+        resv_unassign(sl, list[k].pod, asg_slot(list[k]));
+      }
+    }
+    w = v0;
   }
-  auto resv_ok = [&](const NV &x) {
-    if constexpr (RS > 0) return !(c.filt & KOORDHIP_PLUGIN_RESERVATION) || resv_filter_pre(pod, x, v, nr, mm, nmatch, rp);
+  if constexpr (RS > 0) {
+    if (c.resv) nmatch = resv_restore(w, sl, pod, mm);
+    resv_pre_init(rp, w, sl, pod, mm);
+  }
+  // first: the pass on the row with the nominated pods, whose AddPod lowered the clone's preemptible[node]
+  auto resv_ok = [&](const NV &x, bool first = true) {
+    if constexpr (RS > 0) {
+      if (!(c.filt & KOORDHIP_PLUGIN_RESERVATION)) return true;
+      if constexpr (SEQ_RS) {
+        if (first) {
+          double pe[KOORDHIP_NRES];
+#pragma unroll
+          for (int k = 0; k < KOORDHIP_NRES; k++) pe[k] = rp.pn[k] > ns.r[k] ? rp.pn[k] - ns.r[k] : 0.0;
+          return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp, pe);
+        }
+      }
+      return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp);
+    }
+    return true;
+  };
+  // RunFilterPluginsWithNominatedPods' second pass: the row and the plugin's state without the nominated pods
+  auto second_ok = [&]() {
+    if constexpr (SEQ_RS) {
+      if (ns.n == 0) return true;
+      NV x = w;
+      nom_off(x, ns);
+      return base_status(x) == 0u && amp_ok(x) && resv_ok(x, false);
+    }
     return true;
   };
   if constexpr (OVL) {
-    for (int h = 0; h < 2; h++) {
+    for (int h = 0; h < 2 && !SEQ_RS; h++) {
       uint64_t g = h ? ov.g1 : ov.g0;
       while (g) {
         const int32_t k = (int32_t)__ffsll((unsigned long long)g) - 1 + 64 * h;
@@ -363,9 +447,11 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         }
       }
     }
+    // (SEQ_RS: the nominated pods only now, the frozen podRequested is the snapshot NodeInfo's, which holds none)
     for (int32_t e = ov.head; e >= 0; e = ov.nom[e].next) {
       if (ov.nom[e].prio < pprio) continue;
       apply_delta(w, ov.nom[e].pod, +1);
+      if constexpr (SEQ_RS) nom_add(ns, ov.nom[e].pod);
       if constexpr (DEV > 0) {  // NodeInfo.AddPod counts a nominated pod's scalars (entry e is preemptor e's)
         const DevPodX &nx = ds.px[e];
 #pragma unroll
@@ -498,7 +584,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
     r.status = KOORDHIP_PREEMPT_NO_VICTIMS;
     return r;
   }
-  if (base_status(w) != 0u || !xfit_ok() || !amp_ok(w) || !resv_ok(w) || !dev_ok()) {
+  if (base_status(w) != 0u || !xfit_ok() || !amp_ok(w) || !resv_ok(w) || !dev_ok() || !second_ok()) {
     r.status = KOORDHIP_PREEMPT_UNFIT;
     return r;
   }
@@ -515,7 +601,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       m &= m - 1;
       const DevAsg &a = list[k];
       move(q, a, k, +1);
-      const bool fits = base_status(w) == 0u && xfit_ok() && amp_ok(w) && resv_ok(w) && dev_ok();
+      const bool fits = base_status(w) == 0u && xfit_ok() && amp_ok(w) && resv_ok(w) && dev_ok() && second_ok();
       if (!fits) move(q, a, k, -1);
       bool over = false;
       if (pquota >= 0) {
@@ -969,8 +1055,9 @@ __device__ __forceinline__ DevPre stream_pre(const DevPre *__restrict__ pre, con
 // Block b evaluates preemptor k again iff its rows / lists changed, the
 // budgets changed or k's quota was freed; a block none of this holds for keeps
 // the partial and the counts phase 1 wrote (they depend on nothing else).
-// pl: the plane of all the call's preemptors.
-template <bool NUMA>
+// pl: the plane of all the call's preemptors.  RS > 0 (koordhip_preempt_stream_resv): the walk with the node's
+// reservation slots, run as the per-preemptor chain (StreamFlags::full is set: every block, every preemptor).
+template <bool NUMA, int RS>
 __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
                                                                  const int32_t *__restrict__ off,
                                                                  const DevPre *__restrict__ pre, int32_t k,
@@ -983,7 +1070,7 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, Dev
     return;
   }
   if (t == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&st.stats->block_recomputes), 1ull);
-  const DevCfg c = envelope<NUMA>(cfg);
+  const DevCfg c = envelope<NUMA, RS>(cfg);
   __shared__ int32_t scnt[KOORDHIP_PREEMPT_STATUSES];
   __shared__ PreemptPartial sbest[PRE_WAVES];
   if (t < KOORDHIP_PREEMPT_STATUSES) scnt[t] = 0;
@@ -992,13 +1079,13 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_seq(DevCfg cfg, Dev
   const PdbAllowed pdb = *st.pdb;
   const int32_t i = b * PREEMPT_THREADS + t;
   const bool live = i < d.n;
-  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, live);
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i, live);
   koordhip_preempt_node r{};
   uint32_t fcode = 0u;
   if constexpr (NUMA) fcode = plane_code(pl, k, i);
   if (live)
-    r = preempt_node<EMIT_NONE, true, NUMA>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, nullptr, 0,
-                                            overlay_of(st, i), fcode);
+    r = preempt_node<EMIT_NONE, true, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, nullptr, 0,
+                                                overlay_of(st, i), fcode);
   wave_vote(r, i, live, scnt, &sbest[wave]);
   __syncthreads();
   if (t == 0) st.part[(size_t)k * nb + b] = block_best(sbest);
@@ -1031,16 +1118,17 @@ __global__ __launch_bounds__(64) void k_preempt_seq_pick(int32_t nb, int32_t k, 
 }
 
 // One wave: the chosen node of preemptor k again, its victims written out and
-// taken off the state every later preemptor sees.
-template <bool NUMA>
+// taken off the state every later preemptor sees.  RS > 0: what the victims held of their reservations needs no
+// state of its own, every later walk lowers its slots by the gone positions' records.
+template <bool NUMA, int RS>
 __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
                                                       const int32_t *__restrict__ off, const DevPre *__restrict__ pre,
                                                       int32_t n_pre, int32_t k, StreamState st, int32_t vmax) {
-  const DevCfg c = envelope<NUMA>(cfg);
+  const DevCfg c = envelope<NUMA, RS>(cfg);
   const int lane = threadIdx.x;
   const int32_t i = st.res[k].node;
   if (i < 0 || i >= d.n) return;
-  const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i);  // i is the wave's: scalar loads
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i);  // i is the wave's: scalar loads
   // the node's list into LDS with the whole wave: lane 0's walk is a chain of dependent loads
   __shared__ uint4 slist[KOORDHIP_PREEMPT_NODE_PODS * ASG_VEC];
   const uint4 *src = reinterpret_cast<const uint4 *>(nd.list);
@@ -1052,9 +1140,9 @@ __global__ __launch_bounds__(64) void k_preempt_apply(DevCfg cfg, DevNodes d, co
   __shared__ int64_t ssum[KOORDHIP_PREEMPT_QRES];
   if (lane == 0) {
     PdbAllowed pdb = *st.pdb;
-    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA>(c, d.nu.cls, nd.v, nd.nr, list, nd.len, pdb, P,
-                                                                       st.vpos, KOORDHIP_PREEMPT_NODE_PODS,
-                                                                       overlay_of(st, i), 0u);
+    const koordhip_preempt_node r = preempt_node<EMIT_POS, true, NUMA, RS>(c, d.nu.cls, nd.v, nd.nr, list, nd.len, pdb,
+                                                                           P, st.vpos, KOORDHIP_PREEMPT_NODE_PODS,
+                                                                           overlay_of(st, i), 0u);
     const int32_t nv = r.status == KOORDHIP_PREEMPT_CANDIDATE ? min(r.n_victims, (int32_t)KOORDHIP_PREEMPT_NODE_PODS) : 0;
     uint64_t g0 = 0, g1 = 0;
     int64_t sum[KOORDHIP_PREEMPT_QRES] = {};
@@ -1332,26 +1420,30 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                  int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (m.rs != 0 || m.devp || !preempt_profile_ok(c, m, plane, DevWalk{})) return hipErrorInvalidValue;
+  if (m.devp || !preempt_profile_ok(c, m, plane, DevWalk{})) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
   const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
-  fl.full = full ? 1 : 0;
+  fl.full = full || m.rs > 0 ? 1 : 0;  // with Reservation state: the chain, every block, every preemptor
   hipLaunchKernelGGL(k_stream_init, dim3(1), dim3(64), 0, s, pdb, fl, st);
-  with_walk(m, [&](auto numa, auto) {
+  with_walk(m, [&](auto numa, auto rs) {
     constexpr bool NUMA = decltype(numa)::value;
+    constexpr int RS = decltype(rs)::value;
     const dim3 blocks(nb), threads(PREEMPT_THREADS), wave(64);
     for (int32_t k = 0; k < n_pre; k++) {
       // phase 1 a tile ahead of its first preemptor, not all at once: the loaded state does not change, and a tile
       // launched after the budgets changed costs an empty kernel
-      if (k % PRE_PT == 0)
-        hipLaunchKernelGGL(k_preempt_blk<NUMA>, blocks, threads, 0, s, c, d, tab, off, pdb, pre + k,
-                           std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
-                           st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags,
-                           NUMA ? NumaPlane{plane + (size_t)k * 2 * pl.nw, pl.nw} : pl);
-      hipLaunchKernelGGL(k_preempt_seq<NUMA>, blocks, threads, 0, s, c, d, tab, off, pre, k, st, pl);
+      if constexpr (RS == 0) {
+        if (k % PRE_PT == 0)
+          hipLaunchKernelGGL(k_preempt_blk<NUMA>, blocks, threads, 0, s, c, d, tab, off, pdb, pre + k,
+                             std::min(PRE_PT, n_pre - k), st.part + (size_t)k * nb,
+                             st.bcnt + (size_t)k * nb * KOORDHIP_PREEMPT_STATUSES, st.flags,
+                             NUMA ? NumaPlane{plane + (size_t)k * 2 * pl.nw, pl.nw} : pl);
+      }
+      hipLaunchKernelGGL((k_preempt_seq<NUMA, RS>), blocks, threads, 0, s, c, d, tab, off, pre, k, st, pl);
       hipLaunchKernelGGL(k_preempt_seq_pick, dim3(1), wave, 0, s, nb, k, st);
-      hipLaunchKernelGGL(k_preempt_apply<NUMA>, dim3(1), wave, 0, s, c, d, tab, off, pre, n_pre, k, st, max_victims);
+      hipLaunchKernelGGL((k_preempt_apply<NUMA, RS>), dim3(1), wave, 0, s, c, d, tab, off, pre, n_pre, k, st,
+                         max_victims);
     }
   });
   return hipGetLastError();

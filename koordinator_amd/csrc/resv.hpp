@@ -365,6 +365,26 @@ __device__ __forceinline__ void resv_pre_move(ResvPre<S> &s, const DevPod &a, in
   }
 }
 
+// The sequential dry run: a listed pod bound to slot `slot` (-1: to none) is
+// gone, an earlier preemptor's victim.  RemoveAssignedPod
+// (frameworkext/reservation_info.go:308-319): Allocated =
+// SubtractWithNonNegativeResult(Allocated, Mask(requests, ResourceNames)), the
+// pod leaves AssignedPods.  An AllocateOnce slot keeps its count: one that had
+// an assigned pod is Succeeded (reservation/controller/controller.go:245-247)
+// and never Available again, so it stays class 0 (resv_class) for the call.
+template <int S>
+__device__ __forceinline__ void resv_unassign(NumaRowRS<S> &r, const DevPod &a, int slot) {
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    if (q != slot) continue;
+    ResvSlot &x = r.rs[q];
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+      if (rkey(x.rf, k)) x.rd[k] = x.rd[k] > a.req[k] ? x.rd[k] - a.req[k] : 0.0;
+    if (!(x.rf & KOORDHIP_RESV_ALLOCATE_ONCE)) x.rn = x.rn > 0 ? x.rn - 1 : 0;
+  }
+}
+
 // fitsNode (plugin.go:445-494) on the walk's row w: the pod count of the moved
 // NodeInfo, the frozen podRequested (s.pq; v0: the loaded row, whose ephemeral
 // storage and batch amounts the restore leaves alone), rRemained of the
@@ -386,17 +406,20 @@ __device__ __forceinline__ bool resv_fits_node(const DevPod &p, const NV &w, con
 
 // filterWithReservations (plugin.go:373-440) with the preemptible state s.
 // With nothing present it is resv_filter (nmatch > 0) / the affinity test.
+// pn: state.preemptible[node] as this fit test reads it: s.pn, or in the
+// sequential dry run's first pass the clone's, lowered by AddPod of the node's
+// nominated pods (preempt.hip); s.pr is the same in both.
 template <int S>
 __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
-                                                uint32_t mm, int nmatch, const ResvPre<S> &s) {
-  const bool pn_on = resv_present(s.pn);
+                                                uint32_t mm, int nmatch, const ResvPre<S> &s, const double *pn) {
+  const bool pn_on = resv_present(pn);
   const double none[2] = {0.0, 0.0};
   if (nmatch == 0) {
     if (p.flags & KOORDHIP_POD_RESV_AFFINITY) return false;
     bool any = pn_on;
 #pragma unroll
     for (int q = 0; q < S; q++) any |= resv_present(s.pr[q]);
-    return !any || resv_fits_node(p, w, v0, s, 0, none, none, s.pn);  // a failure: ErrReasonPreemptionFailed
+    return !any || resv_fits_node(p, w, v0, s, 0, none, none, pn);  // a failure: ErrReasonPreemptionFailed
   }
   double rall[2] = {0.0, 0.0};
 #pragma unroll
@@ -415,7 +438,7 @@ __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, co
     const bool pr_on = resv_present(s.pr[q]);
     double pre[KOORDHIP_NRES];
 #pragma unroll
-    for (int k = 0; k < KOORDHIP_NRES; k++) pre[k] = s.pr[q][k] + s.pn[k];
+    for (int k = 0; k < KOORDHIP_NRES; k++) pre[k] = s.pr[q][k] + pn[k];
     const double rem[2] = {rem_of(x, 0), rem_of(x, 1)};  // from the unmodified Allocated
     const bool fits = resv_fits_node(p, w, v0, s, nmatch, rem, rall, pre);
     bool ok = fits;
@@ -436,6 +459,11 @@ __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, co
   }
   if (pass) return true;
   return !((tot[0] > 0 && tot[0] == bad[0]) || (tot[1] > 0 && tot[1] == bad[1]) || (tot[2] > 0 && tot[2] == bad[2]));
+}
+template <int S>
+__device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
+                                                uint32_t mm, int nmatch, const ResvPre<S> &s) {
+  return resv_filter_pre(p, w, v0, r, mm, nmatch, s, s.pn);
 }
 
 // FilterReservation of a matched reservation: a nomination candidate

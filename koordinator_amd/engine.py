@@ -399,7 +399,8 @@ class PlacementEngine:
         preempt_node_verdicts() accept Reservation state: the walk starts from
         the restored row and keeps the plugin's AddPod / RemovePod state
         (listed pods name their reservation slot, preemption.assigned_records);
-        preempt_stream() still refuses it.  The shipped profile needs both;
+        preempt_stream() still refuses it (preempt_stream(resv=True) is the
+        mode's sequential dry run).  The shipped profile needs both;
         on a profile with NodeNUMAResource in the Filter and without the
         Reservation plugin resv=True is refused (KOORDHIP_EINVAL).
         device: preempt() and preempt_node_verdicts() accept a profile whose
@@ -439,7 +440,7 @@ class PlacementEngine:
                                                               max_victims))
         return out, vic
 
-    def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0, ext=None):
+    def preempt_stream(self, preemptors: np.ndarray, max_victims: int = 0, ext=None, resv: bool = False):
         """The dry run of a batch whose answers hold together: the preemptors
         are processed in input order, each on the state the earlier ones left
         (their victims gone, they themselves nominated on their nodes, PDB
@@ -451,13 +452,26 @@ class PlacementEngine:
         sequential dry run of the DeviceShare mode (gone victims' scalars and
         devices are off their nodes, nominated preemptors' scalars on them and
         a nominated pod holds no device); EXT_NULL: that call with all-empty
-        records; None: the plain call, which a DeviceShare profile refuses."""
+        records; None: the plain call, which a DeviceShare profile refuses.
+        resv=True: koordhip_preempt_stream_resv, the sequential dry run of the
+        Reservation mode (preempt_set_mode(resv=True)): gone victims also leave
+        their reservations' Allocated and assigned counts, and a nominated
+        preemptor moves the plugin's state as in the reference's two Filter
+        passes; the plain call keeps refusing Reservation
+        state.  Not together with ext (ValueError)."""
+        if resv and ext is not None:
+            raise ValueError("preempt_stream: resv=True takes no ext records (the DEVICE mode beside Reservation "
+                             "state is not built)")
         pre = np.ascontiguousarray(np.atleast_1d(preemptors), dtype=abi.PREEMPTOR_DTYPE)
         out = np.zeros(len(pre), abi.PREEMPT_RESULT_DTYPE)
         vic = np.full((len(pre), max_victims), -1, np.int32)
         st = np.zeros(1, abi.PREEMPT_STREAM_STATS_DTYPE)
         pv = abi.ptr(vic, C.c_int32) if max_victims else None
-        if ext is None:
+        if resv:
+            self._need("koordhip_preempt_stream_resv")
+            abi.check(self.lib, self.lib.koordhip_preempt_stream_resv(self._ctx, pre.ctypes.data, len(pre),
+                                                                      out.ctypes.data, pv, max_victims, st.ctypes.data))
+        elif ext is None:
             abi.check(self.lib, self.lib.koordhip_preempt_stream(self._ctx, pre.ctypes.data, len(pre), out.ctypes.data,
                                                                  pv, max_victims, st.ctypes.data))
         else:

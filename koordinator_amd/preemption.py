@@ -15,7 +15,11 @@ pods that sit on the nodes, the preemptor records and a view of the result.
 With Reservation state (PlacementEngine.preempt_set_mode(resv=True)) pass
 assigned_records the per-node slot order of the snapshot's reservation columns
 (`reservation_slots`): a listed pod names the slot of the reservation it was
-assumed into, and reserve pods are not listed.
+assumed into, and reserve pods are not listed.  In that mode the batch in
+sequence is PlacementEngine.preempt_stream(pres, resv=True)
+(koordhip_preempt_stream_resv): the earlier preemptors' victims have also left
+their reservations (Allocated and the assigned count, by the slot a record
+names), so the same records serve and nothing is to be pre-subtracted.
 
 PodEligibleToPreemptOthers and nominated pods stay with the caller.
 
