@@ -1129,12 +1129,62 @@ int koordhip_preempt_node_verdicts(koordhip_ctx *ctx, const koordhip_preemptor *
  * KOORDHIP_EINVAL with the flag set: PodTopologySpread or InterPodAffinity in
  * the profile (AddPod / RemovePod state of their own); any Reservation state
  * (the plugin in the Filter or Score, reservation columns, resv_dev_slot
- * columns), with or without KOORDHIP_PREEMPT_RESV: that combination needs
- * preemptibleInRRs and tryAllocateFromReservation and is not built;
+ * columns), with or without KOORDHIP_PREEMPT_RESV, unless
+ * KOORDHIP_PREEMPT_DEVICE_RESV below opted in (cpu / memory reservations only:
+ * device-holding ones need tryAllocateFromReservation and are not built);
  * the plain koordhip_preempt_stream (it takes no koordhip_pod_ext records:
  * the mode's sequential dry run is koordhip_preempt_stream_ext below); what
  * koordhip_preempt refuses besides. */
 #define KOORDHIP_PREEMPT_DEVICE 4u
+/* ---- the dry run under DeviceShare beside Reservation state (additive to ABI 15: detect it by the flag's acceptance)
+ * KOORDHIP_PREEMPT_DEVICE_RESV is the opt-in for the word KOORDHIP_PREEMPT_DEVICE
+ * | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE_RESV (with
+ * KOORDHIP_PREEMPT_NUMA_FROZEN where NodeNUMAResource is in the Filter: the
+ * shipped profile with DeviceShare needs all four).  koordhip_preempt_set_mode
+ * accepts the bit only together with both other bits and on a profile that has
+ * DeviceShare and the Reservation plugin (each in the Filter or Score);
+ * everywhere else a word holding it is KOORDHIP_EINVAL like an unknown bit and
+ * leaves the mode as it was.  With that word koordhip_preempt,
+ * koordhip_preempt_ext, koordhip_preempt_node_verdicts and
+ * koordhip_preempt_node_verdicts_ext accept a profile whose sequential-cycle
+ * plugins are DeviceShare only, reservation columns with up to
+ * KOORDHIP_RESV_SLOTS reservations per node holding cpu / memory, and listed
+ * pods that name a slot (KOORDHIP_ASG_RESV_SLOT) and have a
+ * koordhip_assigned_ext record.  Per (preemptor P, node) the walk is that of
+ * the two modes together, with three rules that exist only where both states do:
+ *   bound victims  DeviceShare's RemovePod / AddPod put a victim bound to a
+ *               reservation into preemptibleInRRs[node][uid], not into
+ *               preemptibleDevices[node] (deviceshare/plugin.go:188-282), and
+ *               without a device-holding reservation nothing reads that map
+ *               (reservation.go:192): Pd moves only for a pod that is NOT bound
+ *               to a slot.  Its scalars still leave NodeInfo.Requested:
+ *               xrequested moves for every listed pod.
+ *   scalars     the Reservation plugin's maps are whole ResourceLists: Pn and
+ *               Pr[q] also hold the listed pods' extended scalars, all
+ *               KOORDHIP_NXRES of them ("has a non-zero request", presence and
+ *               the literal add-back of a bound pod count them), and fitsNode
+ *               tests every scalar j of P's xmask: fail if xreq[j] >
+ *               xalloc[j] - (podRequested.x[j] - pre.x[j]), podRequested.x[j]
+ *               the loaded xrequested[j] on a node with a nodeRState, else 0,
+ *               pre = Pn without a matched slot, Pr[q] + Pn per matched slot.
+ *               NodeResourcesFit reads the moved Requested, fitsNode the frozen
+ *               one: fitsNode is the stricter test whenever a removed pod is
+ *               bound to a reservation other than the one tested.
+ *   order       DeviceShare precedes Reservation in the Filter: a required
+ *               affinity without a match makes the node UNRESOLVABLE only where
+ *               xfit and the DeviceShare Filter pass on the start row too.
+ * count[UNRESOLVABLE] equals koordhip_diagnose_reasons_ext's `unresolvable`.
+ * No reference test pins the bound branch of DeviceShare's RemovePod or
+ * fitsNode's scalar term with something preemptible: parity unpinned, followed
+ * literally.  Still KOORDHIP_EINVAL in this mode: resv_dev_slot / resv_dev /
+ * resv_xalloc columns (device-holding reservations need mergedUnmatchedUsed,
+ * mergedMatchedAllocatable and tryAllocateFromReservation: the follow-up); a
+ * snapshot that places in the sequential cycle by its reservations (more than
+ * KOORDHIP_RESV_SLOTS slots, topology-policy zones); resv_cpus with
+ * KOORDHIP_PREEMPT_NUMA_FROZEN; koordhip_preempt_stream, _stream_ext and
+ * _stream_resv (the sequential dry run under both states is not built); and
+ * what the two modes refuse besides. */
+#define KOORDHIP_PREEMPT_DEVICE_RESV 8u
 int koordhip_preempt_set_mode(koordhip_ctx *ctx, uint32_t flags);
 
 /* What a listed pod holds beyond its koordhip_pod, one record per koordhip_assigned

@@ -338,6 +338,7 @@ PREEMPT_STATUSES = 5
 PREEMPT_NUMA_FROZEN = 1   # koordhip_preempt_set_mode: NodeNUMAResource in the Filter, its verdict frozen for the call
 PREEMPT_RESV = 2          # ... Reservation state: the walk keeps the plugin's AddPod / RemovePod state
 PREEMPT_DEVICE = 4        # ... DeviceShare: the victims' extended scalars and devices move in the walk
+PREEMPT_DEVICE_RESV = 8   # ... both states together: only with RESV | DEVICE, on a profile that has both plugins
 ASSIGNED_DTYPE = np.dtype([
     ("pod", POD_DTYPE), ("node", "<i4"), ("priority", "<i4"), ("start_time", "<i8"), ("quota", "<i4"),
     ("flags", "<u4"), ("pdb_mask", "<u4"), ("reserved", "<u4"), ("qreq", "<i8", (PREEMPT_QRES,)),

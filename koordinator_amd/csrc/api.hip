@@ -3758,8 +3758,18 @@ int koordhip_preempt_load_pods(koordhip_ctx *c, const koordhip_assigned *a, int3
 
 int koordhip_preempt_set_mode(koordhip_ctx *c, uint32_t flags) {
   if (!c) return fail(KOORDHIP_EINVAL, "ctx is NULL");
-  if (flags & ~(KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE))
+  if (flags & ~(KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE | KOORDHIP_PREEMPT_DEVICE_RESV))
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: unknown flag bit");
+  // the opt-in for both states: only beside both modes' bits and where the profile can hold both states
+  if (flags & KOORDHIP_PREEMPT_DEVICE_RESV) {
+    const uint32_t plugins = c->cfg.filter_plugins | c->cfg.score_plugins;
+    if ((flags & (KOORDHIP_PREEMPT_DEVICE | KOORDHIP_PREEMPT_RESV)) != (KOORDHIP_PREEMPT_DEVICE | KOORDHIP_PREEMPT_RESV))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: KOORDHIP_PREEMPT_DEVICE_RESV only together with "
+                                   "KOORDHIP_PREEMPT_DEVICE and KOORDHIP_PREEMPT_RESV");
+    if (!(plugins & KOORDHIP_PLUGIN_DEVICESHARE) || !(plugins & KOORDHIP_PLUGIN_RESERVATION))
+      return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: KOORDHIP_PREEMPT_DEVICE_RESV on a profile without "
+                                   "DeviceShare or without the Reservation plugin");
+  }
   // a profile without DeviceShare can never hold the DEVICE mode's state: the bit is refused like an unknown one
   if ((flags & KOORDHIP_PREEMPT_DEVICE) && !((c->cfg.filter_plugins | c->cfg.score_plugins) & KOORDHIP_PLUGIN_DEVICESHARE))
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_set_mode: KOORDHIP_PREEMPT_DEVICE on a profile without DeviceShare");
@@ -3843,6 +3853,11 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
   if (!c->pre_loaded)
     return fail(KOORDHIP_ESTATE, "koordhip_preempt: no assigned-pod table (koordhip_preempt_load_pods after the last "
                                  "load_snapshot)");
+  if (stream && mode.both)
+    return fail(KOORDHIP_EINVAL, std::string(stream_ext ? "koordhip_preempt_stream_ext"
+                                             : stream_resv ? "koordhip_preempt_stream_resv" : "koordhip_preempt_stream") +
+                                     ": not in the KOORDHIP_PREEMPT_DEVICE_RESV mode (the sequential dry run under "
+                                     "DeviceShare beside Reservation state is the follow-up, not built)");
   if (stream_ext && !mode.dev)
     return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream_ext: only in the KOORDHIP_PREEMPT_DEVICE mode, with records or "
                                  "with ext NULL (elsewhere the sequential dry run is koordhip_preempt_stream)");
@@ -3867,11 +3882,21 @@ static int preempt_ready(koordhip_ctx *c, const koordhip_preemptor *pre, int32_t
     if ((c->cfg.filter_plugins | c->cfg.score_plugins) & (KOORDHIP_PLUGIN_PTS | KOORDHIP_PLUGIN_IPA))
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE not with PodTopologySpread or "
                                    "InterPodAffinity in the profile (they keep AddPod / RemovePod state of their own)");
-    if (mode.resv || c->d.dv.rslot || c->d.dv.rxa)
+    if (mode.both) {
+      if (c->d.dv.rslot || c->d.dv.rxa)
+        return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE_RESV not with resv_dev_slot / resv_dev / "
+                                     "resv_xalloc columns (device-holding reservations need mergedUnmatchedUsed, "
+                                     "mergedMatchedAllocatable and tryAllocateFromReservation: the follow-up, not built)");
+      if (c->seq_snap)
+        return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE_RESV not on a snapshot whose reservations "
+                                     "place in the sequential cycle (more than KOORDHIP_RESV_SLOTS reservations per "
+                                     "node, topology-policy zones)");
+    } else if (mode.resv || c->d.dv.rslot || c->d.dv.rxa)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt: KOORDHIP_PREEMPT_DEVICE not with Reservation state (the plugin in "
                                    "the profile, reservation or resv_dev_slot columns), with or without "
                                    "KOORDHIP_PREEMPT_RESV: that combination (preemptibleInRRs, "
-                                   "tryAllocateFromReservation) is the follow-up, not built");
+                                   "tryAllocateFromReservation) is the follow-up, not built, unless "
+                                   "KOORDHIP_PREEMPT_DEVICE_RESV opted in to cpu / memory reservations");
   } else if (c->seq || c->seq_profile) {
     if (stream && !stream_resv && mode.devp)
       return fail(KOORDHIP_EINVAL, "koordhip_preempt_stream: not under DeviceShare, with or without "

@@ -86,6 +86,8 @@ struct WalkMode {
   bool devp;  // DeviceShare is in the profile (Filter or Score) ...
   int dev;    // ... and the host accepted the walk that moves the victims' extended scalars (1) and, for a call
               // with a device preemptor, their devices (2: the launchers' callers raise 1 to 2 per call); else 0
+  bool both;  // rs > 0 and dev > 0, and the host accepted the walk that keeps both plugins' state
+              // (KOORDHIP_PREEMPT_DEVICE_RESV): without it a mode with both is refused
 };
 inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
   WalkMode m{};
@@ -94,6 +96,7 @@ inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
   m.rs = (pre_mode & KOORDHIP_PREEMPT_RESV) && m.resv ? (c.resv_slots > 1 ? KOORDHIP_RESV_SLOTS : 1) : 0;
   m.devp = ((c.filt | c.score) & KOORDHIP_PLUGIN_DEVICESHARE) != 0;
   m.dev = (pre_mode & KOORDHIP_PREEMPT_DEVICE) && m.devp ? 1 : 0;
+  m.both = (pre_mode & KOORDHIP_PREEMPT_DEVICE_RESV) && m.rs > 0 && m.dev > 0;
   return m;
 }
 
@@ -106,8 +109,9 @@ inline WalkMode preempt_walk_mode(const DevCfg &c, uint32_t pre_mode) {
 // plugin's verdict there and evaluates filterAmplifiedCPUs on every row), else
 // NULL.  With m.rs the walk starts from the restored row and keeps the plugin's
 // AddPod / RemovePod state; DevAsg::flags bits 8-11 name the slot a listed pod
-// is bound to.  With m.dev (rs 0 only) the walk moves the listed pods'
-// extended scalars (1) and devices (2) as dw describes them.
+// is bound to.  With m.dev the walk moves the listed pods' extended scalars
+// (1) and devices (2) as dw describes them; beside m.rs only with m.both, the
+// walk that keeps both states (k_preempt_dev_resv).
 hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab, const int32_t *off,
                           const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, int32_t *count,
                           PreemptPartial *part, koordhip_preempt_node *per_node, const uint64_t *plane, WalkMode m,

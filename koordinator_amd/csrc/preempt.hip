@@ -28,6 +28,10 @@
 //   k_preempt_victims<NUMA, RS>
 //                     one thread per preemptor re-runs its chosen node and
 //                     writes the victims in the reference's append order.
+//   k_preempt_dev<NUMA, DEV> / k_preempt_dev_resv<NUMA, RS, DEV> (and their _victims kernels)
+//                     k_preempt / k_preempt_victims in the DEVICE mode, without
+//                     and with Reservation state: kernels of their own, so that
+//                     the others keep their argument lists and code.
 //   k_preempt_blk<NUMA> / k_preempt_seq<NUMA, RS> / k_preempt_seq_pick / k_preempt_apply<NUMA, RS>
 //                     the sequential dry run (koordhip_preempt_stream): the
 //                     preemptors in input order, each on the state the earlier
@@ -51,13 +55,18 @@
 // RS, run as the chain without phase 1: a walk lowers its copy of the slots by
 // the gone pods and runs both passes of RunFilterPluginsWithNominatedPods on a
 // node with a nominated pod (preempt_node, OVL with RS > 0).
-// DEV > 0 (KOORDHIP_PREEMPT_DEVICE, with RS = 0): the
+// DEV > 0 (KOORDHIP_PREEMPT_DEVICE): the
 // listed pods' extended scalars move with them (1), and for a call with a
 // device preemptor so do their devices (2): DeviceShare's preemptibleDevices
 // per (preemptor, node) as used - Pd in LDS, one column per thread.  In the
 // stream (koordhip_preempt_stream_ext) these are kernels of their own,
 // k_preempt_seq_dev<NUMA, DEV> / k_preempt_apply_dev<NUMA, DEV>, the chain
 // without phase 1; k_preempt_seq_pick is shared.
+// RS > 0 and DEV > 0 (KOORDHIP_PREEMPT_DEVICE_RESV):
+// k_preempt_dev_resv<NUMA, RS, DEV> / k_preempt_victims_dev_resv<NUMA, RS, DEV>
+// over the same tiles and the same walk: the Reservation maps carry the listed
+// pods' extended scalars (resv.hpp ResvPre<S, true>), fitsNode tests the
+// preemptor's, and a victim bound to a slot frees no device.  Not in a stream.
 //
 // Thread-per-node, not wave-per-node: a node's walk is a chain (every Filter
 // reads the row the previous add / remove left), so a wave would hold 63 idle
@@ -328,8 +337,9 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
                                                               int32_t len, const PdbAllowed &pdb, const DevPre &P,
                                                               int32_t *vout, int32_t vmax, const NodeOverlay &ov,
                                                               uint32_t fcode, const DevSide &ds = DevSide{}) {
-  static_assert(DEV == 0 || RS == 0, "the DEVICE mode: not with Reservation state");
+  static_assert(!(OVL && RS > 0 && DEV > 0), "the sequential dry run: not under DeviceShare beside Reservation state");
   constexpr bool SEQ_RS = OVL && RS > 0;  // koordhip_preempt_stream_resv
+  constexpr bool BOTH = RS > 0 && DEV > 0;  // KOORDHIP_PREEMPT_DEVICE_RESV
   koordhip_preempt_node r{};
   const DevPod pod = P.pod;
   // SEQ_RS: the walk's own copies, v0 the loaded row without the gone pods and sl the slots they have left
@@ -383,7 +393,7 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   NV w = v;
   int nmatch = 0;
   uint32_t mm = 0u;
-  ResvPre<(RS > 0 ? RS : 1)> rp;
+  ResvPre<(RS > 0 ? RS : 1), BOTH> rp;
   if constexpr (SEQ_RS) {
     // the gone pods come off the row and the slots before the restore: class, restore and podRequested are those
     // of the lowered slots
@@ -401,7 +411,18 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
   }
   if constexpr (RS > 0) {
     if (c.resv) nmatch = resv_restore(w, sl, pod, mm);
-    resv_pre_init(rp, w, sl, pod, mm);
+    if constexpr (BOTH) {
+      // the restore of cpu / memory-only reservations moves no scalar: podRequested's are the loaded ones
+      int64_t xa[KOORDHIP_NXRES], xq[KOORDHIP_NXRES];
+#pragma unroll
+      for (int j = 0; j < KOORDHIP_NXRES; j++) {
+        xa[j] = ds.dv->xalloc ? ds.dv->xalloc[(size_t)j * ds.n + ds.i] : 0;
+        xq[j] = ds.dv->xreq ? ds.dv->xreq[(size_t)j * ds.n + ds.i] : 0;
+      }
+      resv_pre_init(rp, w, sl, pod, mm, xa, xq);
+    } else {
+      resv_pre_init(rp, w, sl, pod, mm);
+    }
   }
   // first: the pass on the row with the nominated pods, whose AddPod lowered the clone's preemptible[node]
   auto resv_ok = [&](const NV &x, bool first = true) {
@@ -415,7 +436,10 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
           return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp, pe);
         }
       }
-      return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp);
+      if constexpr (BOTH)  // fitsNode also tests P's scalars, on the frozen podRequested and the maps' scalars
+        return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp, ds.x->xreq, ds.x->xmask);
+      else
+        return resv_filter_pre(pod, x, v0, sl, mm, nmatch, rp);
     }
     return true;
   };
@@ -472,17 +496,6 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       return r;
     }
   }
-  if constexpr (RS > 0) {
-    // a required reservation affinity without a matched reservation (plugin.go:378-381) fails whatever is removed;
-    // as the first failing plugin of the start row it is unresolvable
-    if ((c.filt & KOORDHIP_PLUGIN_RESERVATION) && nmatch == 0 && (pod.flags & KOORDHIP_POD_RESV_AFFINITY)) {
-      if (base_status(w) == 0u && amp_ok(w))
-        r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
-      else
-        r.status = any_potential<OVL>(list, len, ov, pprio, pquota) ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
-      return r;
-    }
-  }
   if constexpr (DEV == 2) {
     // the state of the types P requests: used - Pd with Pd empty
     const DevDev &dv = *ds.dv;
@@ -523,10 +536,33 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
       }
     }
   }
+  if constexpr (RS > 0) {
+    // a required reservation affinity without a matched reservation (plugin.go:378-381) fails whatever is removed;
+    // as the first failing plugin of the start row it is unresolvable
+    if ((c.filt & KOORDHIP_PLUGIN_RESERVATION) && nmatch == 0 && (pod.flags & KOORDHIP_POD_RESV_AFFINITY)) {
+      bool first = base_status(w) == 0u && amp_ok(w);
+      // DeviceShare precedes Reservation in the Filter order: it has to pass on the unmoved device state too
+      if constexpr (DEV > 0) first = first && xfit_ok() && dev_ok();
+      if (first)
+        r.status = KOORDHIP_PREEMPT_UNRESOLVABLE;
+      else
+        r.status = any_potential<OVL>(list, len, ov, pprio, pquota) ? KOORDHIP_PREEMPT_UNFIT : KOORDHIP_PREEMPT_NO_VICTIMS;
+      return r;
+    }
+  }
   // list[k] leaves (-1) or rejoins (+1)
   auto move = [&](QuotaUsed &qu, const DevAsg &a, int32_t k, int sign) {
     move_pod(w, qu, a, sign);
-    if constexpr (RS > 0) resv_pre_move(rp, a.pod, asg_slot(a), sign);
+    if constexpr (BOTH) {
+      // The maps are whole ResourceLists: the pod's scalars move with its five resources
+      int64_t axr[KOORDHIP_NXRES];
+#pragma unroll
+      for (int j = 0; j < KOORDHIP_NXRES; j++)
+        axr[j] = (a.flags & ASG_HAS_EXT) && ((ds.xlist[k].xmask >> j) & 1u) ? ds.xlist[k].xreq[j] : 0;
+      resv_pre_move(rp, a.pod, axr, asg_slot(a), sign);
+    } else if constexpr (RS > 0) {
+      resv_pre_move(rp, a.pod, asg_slot(a), sign);
+    }
     if constexpr (DEV > 0) {
       if ((a.flags & ASG_HAS_EXT) && (xm | tm)) {
         const DevAsgX &ax = ds.xlist[k];
@@ -534,9 +570,12 @@ __device__ __forceinline__ koordhip_preempt_node preempt_node(const DevCfg &c, c
         for (int j = 0; j < KOORDHIP_NXRES; j++)
           if ((xm >> j) & 1u) xfree[j] -= sign * ax.xreq[j];
         if constexpr (DEV == 2) {
+          // (BOTH: a bound pod's devices go to DeviceShare's preemptibleInRRs, which nothing reads without a
+          // device-holding reservation: Pd moves for a pod that is not bound only; xfree above moves for both)
+          const bool bound = BOTH && asg_slot(a) >= 0;
 #pragma unroll
           for (int t = 0; t < DT; t++) {
-            const uint32_t sl = ((tm >> t) & 1u) ? ax.dev_slots[t] : 0u;
+            const uint32_t sl = ((tm >> t) & 1u) && !bound ? ax.dev_slots[t] : 0u;
             if (!sl) continue;
 #pragma unroll
             for (int s = 0; s < DS; s++)
@@ -952,6 +991,21 @@ __global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_dev(DevCfg cfg, Dev
   preempt_tiles<false, NUMA, 0, DEV>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl, dw);
 }
 
+// ... under DeviceShare beside Reservation state (KOORDHIP_PREEMPT_DEVICE_RESV): the walk with the node's RS
+// reservation slots, the plugin's maps with their scalars and the DEVICE mode's state, over the same tiles
+template <bool NUMA, int RS, int DEV>
+__global__ __launch_bounds__(PREEMPT_THREADS) void k_preempt_dev_resv(DevCfg cfg, DevNodes d,
+                                                                      const DevAsg *__restrict__ tab,
+                                                                      const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                                      const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                      int32_t *__restrict__ count,
+                                                                      PreemptPartial *__restrict__ part,
+                                                                      koordhip_preempt_node *__restrict__ per_node,
+                                                                      NumaPlane pl, DevWalk dw) {
+  static_assert(RS > 0 && DEV > 0, "both states");
+  preempt_tiles<false, NUMA, RS, DEV>(cfg, d, tab, off, pdb, pre, n_pre, count, part, per_node, nullptr, pl, dw);
+}
+
 // Phase 1 of the sequential dry run: one tile of preemptors on the loaded
 // state (pl: the tile's first preemptor's words).  Once the budgets have
 // changed (or with the A/B knob) every block evaluates every later preemptor
@@ -1018,6 +1072,27 @@ __global__ __launch_bounds__(64) void k_preempt_victims_dev(DevCfg cfg, DevNodes
   const WalkNode<0> nd = load_walk_node<NUMA, 0>(c, d, tab, off, i, true, dw.xtab);
   const DevPre P = pre[p];
   (void)preempt_node<EMIT_IDX, false, NUMA, 0, DEV>(
+      c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, vout + (size_t)p * vmax, vmax, NodeOverlay{}, 0u,
+      dev_side<64>(d, nd.xlist, static_cast<const DevPodX *>(dw.px) + p, su, i));
+}
+
+// ... under DeviceShare beside Reservation state
+template <bool NUMA, int RS, int DEV>
+__global__ __launch_bounds__(64) void k_preempt_victims_dev_resv(DevCfg cfg, DevNodes d, const DevAsg *__restrict__ tab,
+                                                                 const int32_t *__restrict__ off, PdbAllowed pdb,
+                                                                 const DevPre *__restrict__ pre, int32_t n_pre,
+                                                                 const koordhip_preempt_result *__restrict__ res,
+                                                                 int32_t *__restrict__ vout, int32_t vmax, DevWalk dw) {
+  static_assert(RS > 0 && DEV > 0, "both states");
+  const DevCfg c = envelope<NUMA, RS, DEV>(cfg);
+  int64_t *su = dev_state<DEV, 64>();
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n_pre) return;
+  const int32_t i = res[p].node;
+  if (i < 0 || i >= d.n) return;
+  const WalkNode<RS> nd = load_walk_node<NUMA, RS>(c, d, tab, off, i, true, dw.xtab);
+  const DevPre P = pre[p];
+  (void)preempt_node<EMIT_IDX, false, NUMA, RS, DEV>(
       c, d.nu.cls, nd.v, nd.nr, nd.list, nd.len, pdb, P, vout + (size_t)p * vmax, vmax, NodeOverlay{}, 0u,
       dev_side<64>(d, nd.xlist, static_cast<const DevPodX *>(dw.px) + p, su, i));
 }
@@ -1343,10 +1418,11 @@ size_t preempt_plane_words(int32_t n, int32_t n_pre) { return (size_t)std::max(n
 // The launchers' argument check: m is the walk of every state the profile has (the mode with every flag
 // accepted: NodeNUMAResource in the Filter needs the plane, Reservation state the walk with its slots).
 static bool preempt_profile_ok(const DevCfg &c, WalkMode m, const uint64_t *plane, const DevWalk &dw) {
-  const WalkMode all =
-      preempt_walk_mode(c, KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV | KOORDHIP_PREEMPT_DEVICE);
+  const WalkMode all = preempt_walk_mode(c, KOORDHIP_PREEMPT_NUMA_FROZEN | KOORDHIP_PREEMPT_RESV |
+                                                KOORDHIP_PREEMPT_DEVICE | KOORDHIP_PREEMPT_DEVICE_RESV);
   if ((m.dev > 0) != (all.dev > 0) || m.dev > 2) return false;
-  if (m.dev > 0 && (m.rs != 0 || m.resv || !dw.px)) return false;  // DEVICE: no Reservation state, and P's records
+  // DEVICE: P's records, and Reservation state only where the host accepted both (then with the walk's slots)
+  if (m.dev > 0 && (!dw.px || (m.both ? m.rs == 0 : (m.rs != 0 || m.resv)))) return false;
   return m.numa == all.numa && m.rs == all.rs && m.numa == (plane != nullptr);
 }
 
@@ -1382,6 +1458,18 @@ static void with_walk_dev(WalkMode m, F f) {
     devs(std::false_type{});
 }
 
+// ... under both states (m.both): f(std::bool_constant<NUMA>, std::integral_constant<int, RS>,
+// std::integral_constant<int, DEV>), RS in {1, KOORDHIP_RESV_SLOTS}, DEV in {1, 2}.
+template <class F>
+static void with_walk_dev_resv(WalkMode m, F f) {
+  with_walk_dev(m, [&](auto numa, auto dev) {
+    if (m.rs > 1)
+      f(numa, std::integral_constant<int, KOORDHIP_RESV_SLOTS>{}, dev);
+    else
+      f(numa, std::integral_constant<int, 1>{}, dev);
+  });
+}
+
 hipError_t launch_preempt_numa(const DevCfg &c, const DevNodes &d, const DevPre *pre, int32_t n_pre, uint64_t *plane,
                                hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
@@ -1402,6 +1490,13 @@ hipError_t launch_preempt(const DevCfg &c, const DevNodes &d, const DevAsg *tab,
   const dim3 grid(preempt_blocks(d.n), (n_pre + PRE_PT - 1) / PRE_PT);
   if (grid.y > 65535u) return hipErrorInvalidValue;
   const NumaPlane pl{plane, (d.n + 63) / 64};
+  if (m.both) {
+    with_walk_dev_resv(m, [&](auto numa, auto rs, auto dev) {
+      hipLaunchKernelGGL((k_preempt_dev_resv<decltype(numa)::value, decltype(rs)::value, decltype(dev)::value>), grid,
+                         dim3(PREEMPT_THREADS), 0, s, c, d, tab, off, pdb, pre, n_pre, count, part, per_node, pl, dw);
+    });
+    return hipGetLastError();
+  }
   if (m.dev > 0) {
     with_walk_dev(m, [&](auto numa, auto dev) {
       hipLaunchKernelGGL((k_preempt_dev<decltype(numa)::value, decltype(dev)::value>), grid, dim3(PREEMPT_THREADS), 0, s,
@@ -1420,7 +1515,7 @@ hipError_t launch_preempt_stream(const DevCfg &c, const DevNodes &d, const DevAs
                                  const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                  int32_t max_victims, bool full, const uint64_t *plane, WalkMode m, hipStream_t s) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (m.devp || !preempt_profile_ok(c, m, plane, DevWalk{})) return hipErrorInvalidValue;
+  if (m.devp || m.both || !preempt_profile_ok(c, m, plane, DevWalk{})) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
   const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
@@ -1453,7 +1548,7 @@ hipError_t launch_preempt_stream_dev(const DevCfg &c, const DevNodes &d, const D
                                      const PdbAllowed &pdb, const DevPre *pre, int32_t n_pre, const StreamState &st,
                                      int32_t max_victims, const uint64_t *plane, WalkMode m, hipStream_t s, DevWalk dw) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
-  if (m.dev <= 0 || !preempt_profile_ok(c, m, plane, dw)) return hipErrorInvalidValue;
+  if (m.dev <= 0 || m.both || !preempt_profile_ok(c, m, plane, dw)) return hipErrorInvalidValue;
   const int32_t nb = preempt_blocks(d.n);
   const NumaPlane pl{plane, (d.n + 63) / 64};
   StreamFlags fl{};
@@ -1479,7 +1574,13 @@ hipError_t launch_preempt_pick(const DevCfg &c, const DevNodes &d, const DevAsg 
                                int32_t max_victims, WalkMode m, hipStream_t s, DevWalk dw) {
   if (n_pre <= 0 || d.n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_preempt_pick, dim3(n_pre), dim3(64), 0, s, part, preempt_blocks(d.n), count, res);
-  if (victims && max_victims > 0 && m.dev > 0)
+  if (victims && max_victims > 0 && m.both)
+    with_walk_dev_resv(m, [&](auto numa, auto rs, auto dev) {
+      hipLaunchKernelGGL(
+          (k_preempt_victims_dev_resv<decltype(numa)::value, decltype(rs)::value, decltype(dev)::value>),
+          dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims, max_victims, dw);
+    });
+  else if (victims && max_victims > 0 && m.dev > 0)
     with_walk_dev(m, [&](auto numa, auto dev) {
       hipLaunchKernelGGL((k_preempt_victims_dev<decltype(numa)::value, decltype(dev)::value>),
                          dim3((n_pre + 63) / 64), dim3(64), 0, s, c, d, tab, off, pdb, pre, n_pre, res, victims,

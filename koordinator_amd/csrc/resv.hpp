@@ -297,12 +297,27 @@ __device__ __forceinline__ bool resv_filter(const DevPod &p, const NV &v, const 
 // resource is non-zero.  pq / touched: nodeRState.podRequested cpu / memory,
 // the clone taken before the matched restore (transformer.go:129), frozen for
 // the call; a node without a class 1 / 2 slot has no nodeRState (all zero).
-template <int S>
+//
+// X (KOORDHIP_PREEMPT_DEVICE_RESV: DeviceShare beside this state): the maps
+// are whole ResourceLists, so the listed pods' NodeResourcesFit extended
+// scalars move with them: xn / xr[q] beside pn / pr[q], every KOORDHIP_NXRES
+// dimension (the literal add-back of a bound pod compares every resource, also
+// the scalars the preemptor does not request).  xh[j] = Allocatable[j] -
+// podRequested[j] of scalar j, podRequested the loaded xrequested[j] on a node
+// with a nodeRState, else 0: what fitsNode's scalar term leaves free before
+// anything is preemptible.
+template <int S, bool X = false>
 struct ResvPre {
   double pn[KOORDHIP_NRES];
   double pr[S][KOORDHIP_NRES];
   double pq[2];
   bool touched;
+};
+template <int S>
+struct ResvPre<S, true> : ResvPre<S, false> {
+  int64_t xn[KOORDHIP_NXRES];
+  int64_t xr[S][KOORDHIP_NXRES];
+  int64_t xh[KOORDHIP_NXRES];
 };
 
 __device__ __forceinline__ bool resv_present(const double *x) {
@@ -365,6 +380,66 @@ __device__ __forceinline__ void resv_pre_move(ResvPre<S> &s, const DevPod &a, in
   }
 }
 
+// ... with the extended scalars.  xalloc / xrequested: the node's loaded values.
+template <int S>
+__device__ __forceinline__ void resv_pre_init(ResvPre<S, true> &s, const NV &w0, const NumaRowRS<S> &r, const DevPod &p,
+                                              uint32_t mm, const int64_t *xalloc, const int64_t *xrequested) {
+  resv_pre_init(static_cast<ResvPre<S> &>(s), w0, r, p, mm);
+#pragma unroll
+  for (int j = 0; j < KOORDHIP_NXRES; j++) {
+    s.xn[j] = 0;
+    s.xh[j] = xalloc[j] - (s.touched ? xrequested[j] : 0);
+#pragma unroll
+    for (int q = 0; q < S; q++) s.xr[q][j] = 0;
+  }
+}
+
+__device__ __forceinline__ bool resv_present_x(const int64_t *x) {
+  bool on = false;
+#pragma unroll
+  for (int j = 0; j < KOORDHIP_NXRES; j++) on |= x[j] != 0;
+  return on;
+}
+
+// ... ax [KOORDHIP_NXRES]: the listed pod's extended scalars (0 where it holds none).  "Has a non-zero request"
+// counts a scalar; the literal add-back compares the scalars too.
+template <int S>
+__device__ __forceinline__ void resv_pre_move(ResvPre<S, true> &s, const DevPod &a, const int64_t *ax, int slot,
+                                              int sign) {
+  if (!resv_present(a.req) && !resv_present_x(ax)) return;
+  if (slot < 0) {
+#pragma unroll
+    for (int k = 0; k < KOORDHIP_NRES; k++)
+      s.pn[k] = sign < 0 ? s.pn[k] + a.req[k] : (s.pn[k] > a.req[k] ? s.pn[k] - a.req[k] : 0.0);
+#pragma unroll
+    for (int j = 0; j < KOORDHIP_NXRES; j++)
+      s.xn[j] = sign < 0 ? s.xn[j] + ax[j] : (s.xn[j] > ax[j] ? s.xn[j] - ax[j] : 0);
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < S; q++) {
+    if (q != slot) continue;
+    if (sign < 0) {
+#pragma unroll
+      for (int k = 0; k < KOORDHIP_NRES; k++) s.pr[q][k] += a.req[k];
+#pragma unroll
+      for (int j = 0; j < KOORDHIP_NXRES; j++) s.xr[q][j] += ax[j];
+    } else {
+      bool zero = true;
+#pragma unroll
+      for (int k = 0; k < KOORDHIP_NRES; k++) zero &= !(s.pr[q][k] > a.req[k]);
+#pragma unroll
+      for (int j = 0; j < KOORDHIP_NXRES; j++) zero &= !(s.xr[q][j] > ax[j]);
+      if (zero) {
+#pragma unroll
+        for (int k = 0; k < KOORDHIP_NRES; k++) s.pr[q][k] = 0.0;
+#pragma unroll
+        for (int j = 0; j < KOORDHIP_NXRES; j++) s.xr[q][j] = 0;
+      }
+    }
+  }
+}
+
 // The sequential dry run: a listed pod bound to slot `slot` (-1: to none) is
 // gone, an earlier preemptor's victim.  RemoveAssignedPod
 // (frameworkext/reservation_info.go:308-319): Allocated =
@@ -404,22 +479,60 @@ __device__ __forceinline__ bool resv_fits_node(const DevPod &p, const NV &w, con
   return fits;
 }
 
+// What the extended scalars add to filterWithReservations: nothing without them (NoScalars: every existing
+// caller), the X state's presence and fitsNode's scalar term (PreScalars) in the DEVICE_RESV mode.
+// q: a matched slot, -1: the branch without one.
+struct NoScalars {
+  __device__ __forceinline__ bool pn_on() const { return false; }
+  __device__ __forceinline__ bool pr_on(int) const { return false; }
+  __device__ __forceinline__ bool fits(const DevPod &, int) const { return true; }
+};
+// xreq / xm: the preemptor's scalars and their mask.  fitsNode's loop over podRequest.ScalarResources
+// (plugin.go:487-491) with rRemained and allRAllocated holding none: fail if xreq[j] > Allocatable[j] -
+// (podRequested[j] - pre[j]), pre = Pn in the branch without a matched slot, Pr[q] + Pn per matched slot.
+template <int S>
+struct PreScalars {
+  const ResvPre<S, true> &s;
+  const int64_t *xreq;
+  uint32_t xm;
+  __device__ __forceinline__ bool pn_on() const { return resv_present_x(s.xn); }
+  __device__ __forceinline__ bool pr_on(int q) const {
+    bool on = false;
+#pragma unroll
+    for (int k = 0; k < S; k++) on |= k == q && resv_present_x(s.xr[k]);
+    return on;
+  }
+  __device__ __forceinline__ bool fits(const DevPod &p, int q) const {
+    if (!(p.flags & KOORDHIP_POD_HAS_REQ)) return true;  // (fitsNode returns before its resource tests)
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < KOORDHIP_NXRES; j++) {
+      int64_t pre = s.xn[j];
+#pragma unroll
+      for (int k = 0; k < S; k++) pre += k == q ? s.xr[k][j] : 0;
+      ok &= !(((xm >> j) & 1u) && xreq[j] > s.xh[j] + pre);
+    }
+    return ok;
+  }
+};
+
 // filterWithReservations (plugin.go:373-440) with the preemptible state s.
 // With nothing present it is resv_filter (nmatch > 0) / the affinity test.
 // pn: state.preemptible[node] as this fit test reads it: s.pn, or in the
 // sequential dry run's first pass the clone's, lowered by AddPod of the node's
-// nominated pods (preempt.hip); s.pr is the same in both.
-template <int S>
+// nominated pods (preempt.hip); s.pr is the same in both.  xs: the scalars' side.
+template <int S, class XS = NoScalars>
 __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
-                                                uint32_t mm, int nmatch, const ResvPre<S> &s, const double *pn) {
-  const bool pn_on = resv_present(pn);
+                                                uint32_t mm, int nmatch, const ResvPre<S> &s, const double *pn,
+                                                const XS &xs = XS{}) {
+  const bool pn_on = resv_present(pn) || xs.pn_on();
   const double none[2] = {0.0, 0.0};
   if (nmatch == 0) {
     if (p.flags & KOORDHIP_POD_RESV_AFFINITY) return false;
     bool any = pn_on;
 #pragma unroll
-    for (int q = 0; q < S; q++) any |= resv_present(s.pr[q]);
-    return !any || resv_fits_node(p, w, v0, s, 0, none, none, pn);  // a failure: ErrReasonPreemptionFailed
+    for (int q = 0; q < S; q++) any |= resv_present(s.pr[q]) || xs.pr_on(q);
+    return !any || (resv_fits_node(p, w, v0, s, 0, none, none, pn) && xs.fits(p, -1));  // a failure: ErrReasonPreemptionFailed
   }
   double rall[2] = {0.0, 0.0};
 #pragma unroll
@@ -435,12 +548,13 @@ __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, co
     if (!((mm >> q) & 1u)) continue;
     const ResvSlot &x = r.rs[q];
     const uint32_t pol = KOORDHIP_RESV_POLICY(x.rf);
-    const bool pr_on = resv_present(s.pr[q]);
+    // (an entry present by a scalar alone holds zero cpu / memory: Restricted's max0(Allocated - 0) is Allocated)
+    const bool pr_on = resv_present(s.pr[q]) || xs.pr_on(q);
     double pre[KOORDHIP_NRES];
 #pragma unroll
     for (int k = 0; k < KOORDHIP_NRES; k++) pre[k] = s.pr[q][k] + pn[k];
     const double rem[2] = {rem_of(x, 0), rem_of(x, 1)};  // from the unmodified Allocated
-    const bool fits = resv_fits_node(p, w, v0, s, nmatch, rem, rall, pre);
+    const bool fits = resv_fits_node(p, w, v0, s, nmatch, rem, rall, pre) && xs.fits(p, q);
     bool ok = fits;
     if (pol == 0) {
       ok = !(pr_on || pn_on) || fits;
@@ -464,6 +578,14 @@ template <int S>
 __device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
                                                 uint32_t mm, int nmatch, const ResvPre<S> &s) {
   return resv_filter_pre(p, w, v0, r, mm, nmatch, s, s.pn);
+}
+// ... with the extended scalars (the DEVICE_RESV mode): the preemptor's xreq [KOORDHIP_NXRES] and xmask
+template <int S>
+__device__ __forceinline__ bool resv_filter_pre(const DevPod &p, const NV &w, const NV &v0, const NumaRowRS<S> &r,
+                                                uint32_t mm, int nmatch, const ResvPre<S, true> &s,
+                                                const int64_t *xreq, uint32_t xm) {
+  return resv_filter_pre(p, w, v0, r, mm, nmatch, static_cast<const ResvPre<S> &>(s), s.pn,
+                         PreScalars<S>{s, xreq, xm});
 }
 
 // FilterReservation of a matched reservation: a nomination candidate

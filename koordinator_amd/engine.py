@@ -391,7 +391,8 @@ class PlacementEngine:
             raise ValueError("one koordhip_pod_ext record per preemptor")
         return x
 
-    def preempt_set_mode(self, numa_frozen: bool = False, resv: bool = False, flags: int = None, device: bool = False):
+    def preempt_set_mode(self, numa_frozen: bool = False, resv: bool = False, flags: int = None, device: bool = False,
+                         device_resv: bool = False):
         """numa_frozen: the dry-run calls accept NodeNUMAResource in the Filter,
         with the plugin's verdict frozen for the call: victims' cpusets and
         zone amounts are not freed and a nominated cpuset preemptor holds no
@@ -410,12 +411,22 @@ class PlacementEngine:
         DeviceShare, with PodTopologySpread / InterPodAffinity or Reservation
         state, and by preempt_stream() without ext (preempt_stream(ext=...) is
         the mode's sequential dry run).
+        device_resv: the opt-in for DeviceShare beside Reservation state, only
+        together with resv=True and device=True (and numa_frozen=True where
+        NodeNUMAResource filters: the shipped profile with DeviceShare needs
+        all four) and on a profile that has both plugins, KOORDHIP_EINVAL
+        elsewhere: preempt() and preempt_node_verdicts() then accept cpu /
+        memory reservations beside device columns, listed pods that name a slot
+        and have an ext record; a bound victim's devices are not freed, the
+        plugin's maps carry the extended scalars (include/koordhip.h).
+        Device-holding reservations and preempt_stream() stay refused.
         The mode is the context's; False restores the refusal.  flags: the raw
         abi.PREEMPT_* word instead."""
         if not hasattr(self.lib, "koordhip_preempt_set_mode"):
             raise RuntimeError("this libkoordhip build has no koordhip_preempt_set_mode")
         word = ((abi.PREEMPT_NUMA_FROZEN if numa_frozen else 0) | (abi.PREEMPT_RESV if resv else 0) |
-                (abi.PREEMPT_DEVICE if device else 0)) if flags is None else int(flags)
+                (abi.PREEMPT_DEVICE if device else 0) |
+                (abi.PREEMPT_DEVICE_RESV if device_resv else 0)) if flags is None else int(flags)
         abi.check(self.lib, self.lib.koordhip_preempt_set_mode(self._ctx, word))
 
     def preempt(self, preemptors: np.ndarray, max_victims: int = 0, ext=None):

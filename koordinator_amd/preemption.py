@@ -181,10 +181,22 @@ def preemptor_records(pods: Iterable[k8s.Pod], profile: Profile, quotas: QuotaId
     return out
 
 
-def assigned_ext_records(pods: Iterable[k8s.Pod], table, node_index: Dict[str, int]) -> np.ndarray:
+def assigned_ext_records(pods: Iterable[k8s.Pod], table, node_index: Dict[str, int],
+                         reservation_slots: Optional[Dict[int, List[Reservation]]] = None) -> np.ndarray:
     """abi.ASSIGNED_EXT_DTYPE records beside assigned_records' (the same pods in
     the same order: those bound to a node of `node_index`), for the dry run
-    under DeviceShare (PlacementEngine.preempt_set_mode(device=True)):
+    under DeviceShare (PlacementEngine.preempt_set_mode(device=True)).
+    `reservation_slots`: what assigned_records was given (only whether it is
+    None is read): with it reserve pods are skipped here as well, so that the
+    two tables stay parallel.  Under DeviceShare beside Reservation state
+    (preempt_set_mode(numa_frozen=..., resv=True, device=True, device_resv=True)):
+
+        slots = reservation.available_by_node(...)        # as for reservation_columns
+        a, pdb, keys = assigned_records(pods, prof, node_index, quotas, pdbs, reservation_slots=slots)
+        ax = assigned_ext_records(pods, table, node_index, reservation_slots=slots)
+        engine.preempt_load_pods(a, pdb, ext=ax)
+
+    A record's fields:
 
       xreq / xmask          deviceshare.fit_xreq: the extended scalars
                             NodeInfo.RemovePod / AddPod move
@@ -198,6 +210,8 @@ def assigned_ext_records(pods: Iterable[k8s.Pod], table, node_index: Dict[str, i
     type (plugin.go:465-478 allocates that way)."""
     from . import deviceshare as ds
     pods = [p for p in pods if p.node_name in node_index]
+    if reservation_slots is not None:
+        pods = [p for p in pods if not is_reserve_pod(p)]
     out = np.zeros(len(pods), abi.ASSIGNED_EXT_DTYPE)
     for j, pod in enumerate(pods):
         rec = out[j]
